@@ -9,12 +9,14 @@ A step = forward + 13-term loss + backward + gradient all-reduce (RCCL, N>1) + g
 KITTI-shaped batch that is resident in HBM before the timed region.  The metric's batch is GLOBAL: with N > 1 the 8 images
 are split over the ranks as the reference does (IMS_PER_BATCH // world, DGDE/data/build.py:63-67: one image per rank at
 N = 8, north_star's partition), value = 8 images / max-over-ranks step time, "scaling": "strong" -- the default since
-round 3.  The same run then also times 8 images PER rank (BASELINE.json configs[2] is that at N = 4: bs 32 on 4 GPUs) and
-reports it under the extra key "weak_scaling"; `--scaling weak` makes that the headline instead (metric string says so).
+round 3.  With `--full` the same run then also times 8 images PER rank (BASELINE.json configs[2] is that at N = 4: bs 32 on
+4 GPUs) and reports it under the extra key "weak_scaling"; `--scaling weak` makes that the headline instead (metric string says so).
 At <= 2 images per rank the step is launch-bound and is replayed from ONE HIP graph that contains the SyncBN and gradient
 collectives (engine.trainer.GraphedTrainStep(distributed=True)); DCD_STEP_GRAPH=0 keeps the eager DDP step.
 
-One JSON line on rank 0.  Besides the driver's contract it carries
+One JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline keys (metric, value, unit,
+ms_per_step, dtype, config ...) and nothing else.  `--dump-outputs DIR` writes what the timed path computes from the seeded
+inputs as DIR/<name>.npy (dump_outputs).  With `--full` the line also carries
   roofline     -- DCNv2 forward+backward of the 16 DLA-34 DCN layers: GEMM flops (computed from the
                   layer list below) / time of those calls measured with events on the launch stream, inside the timed
                   steps; peak = the fp32 matrix peak (the op is MFMA-bound: 196 FLOP/B).  `roofline_hbm` repeats it with
@@ -24,8 +26,10 @@ One JSON line on rank 0.  Besides the driver's contract it carries
                   3x3 convolutions' forward / input gradient in split-bf16 (hi*hi + hi*lo + lo*hi on the bf16 matrix cores, fp32
                   accumulate; <= 1e-4 of the output scale against the fp32 oracle, north_star's bound is 1e-3).  `value` is always
                   the exact-fp32 run.
+  (and mixed_bf16, roofline_op_*, step_2px, weak_scaling at N > 1: see run_gpu)
 """
 import argparse
+import copy
 import json
 import os
 
@@ -188,6 +192,49 @@ def op_level_lines(torch, ext, batch, prec):
     return out
 
 
+DUMP_SAMPLE = 1 << 20          # entries of the parameter / gradient sample that --dump-outputs writes (4 MiB each)
+
+
+def restore_seeded_state(torch, model, optimizer, state):
+    """Parameters and BN buffers back to `state`, the optimizer to its state before the first step (moments and step counters
+    zero) -- both in place, as GraphedTrainStep restores them after its warm-up: a captured graph keeps addressing these tensors."""
+    getattr(model, "module", model).load_state_dict(state)
+    with torch.no_grad():
+        for st in optimizer.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+
+
+def dump_outputs(torch, directory, model, loss_dict, log):
+    """`--dump-outputs DIR`: what the timed path (the same `step()`: eager step or graph replay) computes from the benchmark's
+    seeded inputs -- the batch, and the model and optimizer as set up -- in one step run after everything else.  It is not the
+    last timed step itself: that step's inputs are the state after W + N - 1 training steps, which is not the same from run to
+    run (the backward sums some gradients with fp32 atomics, and AdamW at lr 3e-3 turns those last-bit differences into loss
+    differences of a few percent within three steps: DESIGN.md section 5).  The step returns (loss_dict, log) and updates the
+    model in place, so DIR gets
+      loss_<name>.npy   every term of the loss dict, shape (1,)
+      log_<name>.npy    every entry of the log dict, shape (1,)
+      params.npy        a fixed sample of the updated parameters: DUMP_SAMPLE positions of all parameters flattened in
+                        named_parameters() order, drawn once from torch.randperm with seed 0 (the same for every run)
+      grads.npy         the gradients of the step at the same positions (0 where a parameter got no gradient)"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(directory, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    for k, v in loss_dict.items():
+        save("loss_" + k, torch.as_tensor(v).reshape(1))
+    for k, v in log.items():
+        save("log_" + k, torch.as_tensor(v).reshape(1))
+    params = [p for _, p in getattr(model, "module", model).named_parameters()]
+    total = sum(p.numel() for p in params)
+    pick = torch.randperm(total, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(params[0].device)
+    with torch.no_grad():
+        save("params", torch.cat([p.reshape(-1) for p in params])[pick])
+        save("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])[pick])
+
+
 def build_everything(args, device, world, local_rank):
     import torch
     from dcd_amd import _ext
@@ -248,7 +295,9 @@ def run_gpu(args):
     torch.backends.cudnn.benchmark = os.environ.get("DCD_MIOPEN_FIND", "0") == "1"
 
     cfg, model, optimizer, images, targets, per_rank, use_graph, data_parallel = build_everything(args, device, world, local_rank)
-    timer = DcnTimer(torch, _ext)
+    # --dump-outputs: the seeded state the run starts from, to run the timed path once more from it at the end (dump_outputs)
+    seeded = copy.deepcopy(getattr(model, "module", model).state_dict()) if args.dump_outputs else None
+    timer = DcnTimer(torch, _ext) if args.full else None
     clip = cfg.SOLVER.GRAD_NORM_CLIP
 
     # Whole step replayed from ONE HIP graph (engine.trainer.GraphedTrainStep): see build_everything for when.  At bs 8 on one
@@ -275,17 +324,17 @@ def run_gpu(args):
 
             if args.recapture_every:
                 def step():
-                    graphed(images, targets)                 # __call__: re-captures every N replays (all ranks count the same calls)
+                    return graphed(images, targets)          # __call__: re-captures every N replays (all ranks count the same calls)
             else:
                 def step():
-                    graphed.replay(images, targets)
+                    return graphed.replay(images, targets)
         else:
             use_graph = False
             if data_parallel:
                 model = wrap_distributed(model, cfg, local_rank)
     if not use_graph:
         def step():
-            train_step(model, optimizer, images, targets, clip)
+            return train_step(model, optimizer, images, targets, clip)
     trace = (lambda m: (sys.stderr.write("[bench] %s\n" % m), sys.stderr.flush())) if os.environ.get("DCD_BENCH_TRACE") else (lambda m: None)
     for i in range(args.warmup):
         step()
@@ -300,16 +349,18 @@ def run_gpu(args):
         torch.cuda.synchronize()
 
     fence()
-    timer.enabled = not use_graph
+    if timer is not None:
+        timer.enabled = not use_graph
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
     trace("timed region done")
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
     dcn_source = "event pairs around every DCN call inside the timed steps"
-    if use_graph:
+    if args.full and use_graph:
         # kernels inside a graph replay cannot be bracketed by events: the DCN time comes from eager steps of the same model
         # and batch, run right after the timed region (same process, same clocks)
         # (one untimed eager step first: allocator blocks of the eager step's sizes, DCN hand-over reports).  Under data
@@ -326,7 +377,7 @@ def run_gpu(args):
         dcn_source = ("event pairs around every DCN call in %d eager steps run right after the timed (graph-replayed) region%s"
                       % (args.dcn_steps, "; host-bound under data parallelism: includes launch gaps, an upper bound" if data_parallel else ""))
     offsets = None
-    if rank == 0 and not (isinstance(model, torch.nn.parallel.DistributedDataParallel) or data_parallel):
+    if args.full and rank == 0 and not (isinstance(model, torch.nn.parallel.DistributedDataParallel) or data_parallel):
         # one eager FORWARD of the same model and batch, outside the timed region (no collectives involved: single-process runs only)
         with OffsetStats(torch, _ext) as st, torch.no_grad():
             model(images, targets)
@@ -344,10 +395,7 @@ def run_gpu(args):
     # the fused DCN op has 196 FLOP per algorithmic byte: above the fp32 matrix ridge (157.3 TF / 8 TB/s = 19.7), below the bf16
     # one (2 500 / 8 = 312) -- in mixed precision HBM is the roofline that bounds it
     hbm_bound = prec == "bf16"
-    dcn_count = args.dcn_steps if use_graph else args.steps
-    dcn_ms = timer.total_ms() / max(dcn_count, 1)                       # per step, this rank's share of the batch
     by, fl = dcn_algorithmic(per_rank)
-    traffic, mfma_busy, pmc_source, pmc_commit = load_pmc(per_rank, prec)
     out = None
     if rank == 0:
         out = {
@@ -362,6 +410,12 @@ def run_gpu(args):
                        "global_batch": global_batch, "per_gpu_batch": per_rank, "input": size_hw,
                        "parallelism": "dp%d" % world, "dcn_precision": prec, "step_launch": step_launch,
                        "sync_bn": bool(data_parallel)},
+        }
+    if out is not None and args.full:
+        dcn_count = args.dcn_steps if use_graph else args.steps
+        dcn_ms = timer.total_ms() / max(dcn_count, 1)                   # per step, this rank's share of the batch
+        traffic, mfma_busy, pmc_source, pmc_commit = load_pmc(per_rank, prec)
+        out.update({
             # The fused op has 196 FLOP per algorithmic byte (ridge of the part: 157.3 TF / 8 TB/s = 19.7), so the matrix pipe
             # is the bound that applies; the HBM view north_star also asks for is kept beside it.
             "roofline": {"bound": "hbm" if hbm_bound else "mfma", "kernel": "DCNv2 fwd+bwd, 16 layers, batch %d per GPU" % per_rank,
@@ -389,13 +443,14 @@ def run_gpu(args):
             "roofline_hbm": {"bound": "hbm", "achieved": by / 1e9 / (dcn_ms / 1e3) if dcn_ms > 0 else None, "peak": HBM_PEAK_GBS,
                              "unit": "GB/s", "frac": (by / 1e9 / (dcn_ms / 1e3)) / HBM_PEAK_GBS if dcn_ms > 0 else None,
                              "algorithmic_bytes": by},
-        }
-    if out is not None and world == 1 and not args.amp and not args.no_op_line:
+        })
+    if out is not None and args.full and world == 1 and not args.amp and not args.no_op_line:
         out.update(op_level_lines(torch, _ext, per_rank, args.precision))
     # The same job with the DCN contractions in split-bf16 (DCD_PREC_BF16X3: hi*hi + hi*lo + lo*hi on the bf16 matrix cores, fp32
     # accumulate, ~2^-16 relative per product against north_star's 1e-3 bound) as an EXTRA object: `value` above stays the exact
     # fp32 run.  One GPU, eager step only (a captured graph has the fp32 kernels baked in).
-    if out is not None and world == 1 and not use_graph and not args.amp and args.precision == "f32" and not args.no_split_line:
+    if (out is not None and args.full and world == 1 and not use_graph and not args.amp and args.precision == "f32"
+            and not args.no_split_line):
         # ... and in mixed precision (DCD_PREC_BF16, what MODEL.FP16 / --amp selects: ONE product of bf16-rounded operands, fp32
         # accumulate and storage): BASELINE config 3's arithmetic on this box, next to the fp32 number it is compared with
         for key, pname in (("split_bf16x3", "bf16x3"), ("mixed_bf16", "bf16")):
@@ -428,8 +483,8 @@ def run_gpu(args):
     # op test samples at 2 * randn px (DGDE/model/backbone/DCNv2/DCN/testcuda.py:73).  A second model, same architecture, batch and
     # seed with conv_offset_mask ~ N(0, std^2), std chosen so that mean |offset| is ~1.6 px (= E|2 randn|): what the step costs when
     # the offsets have grown.  One GPU, eager step, fp32.
-    if (out is not None and world == 1 and not use_graph and not args.amp and args.precision == "f32" and not args.no_split_line
-            and args.offset_std_2px > 0):
+    if (out is not None and args.full and world == 1 and not use_graph and not args.amp and args.precision == "f32"
+            and not args.no_split_line and args.offset_std_2px > 0):
         import argparse as _ap
         a2 = _ap.Namespace(**vars(args))
         a2.offset_std = args.offset_std_2px
@@ -460,7 +515,7 @@ def run_gpu(args):
     # N > 1, north_star's split as the headline: the weak-scaling number of the same job (8 images per rank, eager DDP step with
     # bucketed all-reduce overlapped with the backward) as an extra key -- what BASELINE.json configs[2] is at N = 4
     test_weak = force_ddp and os.environ.get("DCD_TEST_WEAK") == "1"        # one-GPU rehearsal of this branch (twice the batch)
-    if (world > 1 or test_weak) and args.scaling == "strong" and not args.no_weak:
+    if args.full and (world > 1 or test_weak) and args.scaling == "strong" and not args.no_weak:
         from dcd_amd.data.synthetic import make_batch
         from dcd_amd.engine.trainer import wrap_distributed
         w_batch = args.batch * (2 if test_weak else 1)
@@ -488,6 +543,13 @@ def run_gpu(args):
             out["weak_scaling"] = {"value": w_batch * world * w_steps / float(w_el.item()), "unit": "images/s", "scaling": "weak",
                                    "global_batch": w_batch * world, "per_gpu_batch": w_batch, "steps": w_steps,
                                    "ms_per_step": 1e3 * float(w_el.item()) / w_steps, "step_launch": step_launch}
+    if seeded is not None:                           # every rank: the step holds the collectives under data parallelism
+        restore_seeded_state(torch, model, optimizer, seeded)
+        res = step()
+        fence()
+        if rank == 0:
+            dump_outputs(torch, args.dump_outputs, model, *res)
+        del res
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
@@ -979,7 +1041,17 @@ def main():
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-serial-dcn-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry", action="store_true", help="exercise the multi-rank launch path on the host (gloo), no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: DCN roofline and per-layer times, op-level DCN lines, the "
+                         "split-bf16 / mixed-bf16 / 2 px re-timings, weak scaling (N > 1) and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="at the end, write what the timed path computes from the seeded inputs (one more step from the initial "
+                         "model and optimizer state) as DIR/<name>.npy, float32; see dump_outputs")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry or args.workload != "dgde"):
+        ap.error("--dump-outputs writes the outputs of the dgde train step (not of --dry, --workload gmw or --workload gen)")
+    if args.steps < 1 and not args.dry:
+        ap.error("--steps must be at least 1")
     if args.cpu_serial_dcn_child:
         cpu_serial_dcn_child(args)
         return
@@ -996,7 +1068,7 @@ def main():
     out = run_dry(args) if args.dry else run_gmw(args) if args.workload == "gmw" else run_gen(args) if args.workload == "gen" else run_gpu(args)
     sys.stdout.flush()
     if out is not None:
-        if args.gpus == 1 and not args.no_cpu_baseline and not args.dry:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline and not args.dry:
             out["cpu_baseline"] = cpu_baseline(args)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
