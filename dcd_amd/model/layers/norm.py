@@ -7,7 +7,8 @@ DGDE/model/backbone/dla_dcn.py:17-18), so checkpoints are interchangeable.  `for
 
 Device tensors always take the HIP kernels (and raise if libdcd_hip.so is missing).  CPU tensors (the host-logic tests)
 run `torch.nn.BatchNorm2d.forward`, the very op the reference calls; synchronised statistics exist on the device only --
-the world-size-2 gloo tests plug their own torch restatement into `BatchNorm2d.host_sync_stats` (tests/cpu_syncbn.py).
+the world-size-2 gloo tests plug their own torch restatement into `BatchNorm2d.host_sync_stats` (tests/cpu_syncbn.py); the
+device path itself is tested at world sizes 2 to 8 on one GPU, the ranks run one after the other (tests/test_gpu_syncbn.py).
 `sync_group`: set by `engine.trainer.wrap_distributed` when MODEL.USE_SYNC_BN; statistics are then all-reduced.
 """
 import torch

@@ -1,6 +1,7 @@
 """Fused BN (+residual) (+ReLU) HIP kernels (csrc/norm.hip) against the stock torch ops the reference uses
 (F.batch_norm + add + relu and their autograd), evaluated in fp64 on the same inputs.
-Tolerance: 2e-5 of each tensor's max magnitude (fp32 arithmetic; the task's bound for floating point is 1e-3)."""
+Tolerance: 2e-5 of each tensor's max magnitude (fp32 arithmetic; the task's bound for floating point is 1e-3).
+The synchronised (split) forms of the same kernels at world size > 1: tests/test_gpu_syncbn.py."""
 import pytest
 import torch
 from torch.nn import functional as F
