@@ -142,6 +142,7 @@ SIGNATURES = {
     "dcd_loss_rows_backward": (c_int, [c_void_p, ctypes.POINTER(LossRowsArgs)]),
     "dcd_loss_rows_finish": (c_int, [c_void_p, ctypes.POINTER(LossRowsArgs)]),
     "dcd_encode_targets": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_double] * 3 + [c_int, c_int, c_void_p, c_int]),
+    "dcd_preprocess_images": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

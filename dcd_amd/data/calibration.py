@@ -1,7 +1,7 @@
 """Camera calibration holder with the attributes the hot path reads from the reference's `Calibration`
 (DGDE/data/datasets/kitti_utils.py:186-248: P, c_u, c_v, f_u, f_v, b_x, b_y) and its image->camera
 back-projection (`project_image_to_rect`, kitti_utils.py:399-418).  Built from a 3x4 matrix instead of a
-KITTI calib file (inputs are synthetic here; file parsing is data-pipeline code, out of scope)."""
+KITTI calib file: `dcd_amd/data/kitti_files.py` reads `P2` from `calib/*.txt`, `dcd_amd/data/synthetic.py` uses the matrix below."""
 import numpy as np
 import torch
 

@@ -656,6 +656,28 @@ int dcd_encode_targets(void *stream, const double *objs, const double *kpts3d, c
                        int n_outputs);
 
 /* ------------------------------------------------------------------------------------------------
+ * The image half of the input pipeline on the device (csrc/images.hip): B decoded uint8 frames of different sizes -> the
+ * network's input batch, one launch.  Replaces, per sample, the image side of `RandomHorizontallyFlip`
+ * (DGDE/data/augmentations/augmentations.py:33-36), `KITTIDataset.pad_image` (DGDE/data/datasets/kitti.py:262-272) and
+ * `ToTensor` + `Normalize` with `TO_BGR` (DGDE/data/transforms/transforms.py:14-30, transforms/build.py,
+ * INPUT.PIXEL_MEAN / PIXEL_STD / TO_BGR).
+ *   src      one device buffer of src_bytes bytes holding the frames: packed uint8 RGB, HWC, rows `pitch` bytes apart
+ *   images   (B, 5) int64 on the device, per image: byte offset of its first pixel in src, row pitch in bytes (>= 3 w),
+ *            height, width (each <= in_h / in_w), flip (0 / 1: mirror the columns).  An image whose record does not lie inside
+ *            [0, src_bytes) or exceeds the canvas is read as empty (all border); nothing outside src is ever read.
+ *   table    (3, 256) fp32 on the device: table[k][v] = the normalised value of byte v in SOURCE channel k, built by the caller
+ *            with the reference's own operations (`arange(256, dtype=uint8).float().div(255).sub(mean[k]).div(std[k])`), so the
+ *            kernel has no arithmetic of its own and the output is bit-equal to the reference's.
+ *   out      (B, 3, in_h, in_w) fp32, fully overwritten.  With pad_x = (in_w - w) / 2, pad_y = (in_h - h) / 2 (kitti.py:266-267):
+ *            out[b][c][y][x] = table[k][v], k = to_bgr ? 2 - c : c, v = byte k of the source pixel at row y - pad_y, column
+ *            x - pad_x (flip: w - 1 - (x - pad_x)), or 0 outside the image -- the reference pads the uint8 canvas before it
+ *            normalises and normalises before it permutes the planes.
+ * 16-byte stores when in_w % 4 == 0 and out is 16-byte aligned, scalar stores otherwise; same results.  No workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_preprocess_images(void *stream, const uint8_t *src, int64_t src_bytes, const int64_t *images, const float *table, int B,
+                          int in_h, int in_w, int to_bgr, float *out);
+
+/* ------------------------------------------------------------------------------------------------
  * The optimizer end of the train step (csrc/optim.hip): `torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)` followed by
  * `AdamW.step()` (DGDE/engine/trainer.py:144-147; DGDE/solver/__init__.py:10-62: AdamW, betas (0.9, 0.99), one learning rate per
  * parameter) over LISTS of fp32 tensors.  The host arrays of pointers / element counts are read during the call only (they travel
