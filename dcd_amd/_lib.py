@@ -39,6 +39,14 @@ class HeadRowsArgs(ctypes.Structure):
                    ("grad_bias", c_void_p * HEADS_MAX)])
 
 
+class EvalMatchArgs(ctypes.Structure):
+    """`dcd_eval_match_args` of include/dcd_hip.h, field for field."""
+    _INTS = ("mode", "n_img", "n_comb", "n_rows", "G", "D", "n_dc", "max_dt", "T", "n_slots")
+    _POINTERS = ("gt_off", "dt_off", "dc_off", "pair_off", "overlaps", "ign_gt", "ign_dt", "dt_score", "gt_alpha", "dt_alpha",
+                 "dt_box2d", "dc_box", "comb", "min_overlap", "thresholds", "n_thresh", "scores", "counts", "sim_part")
+    _fields_ = [(n, c_int) for n in _INTS] + [("P", c_int64)] + [(n, c_void_p) for n in _POINTERS]
+
+
 # name -> (restype, argtypes); mirrors include/dcd_hip.h one to one
 SIGNATURES = {
     "dcd_version": (ctypes.c_char_p, []),
@@ -143,6 +151,9 @@ SIGNATURES = {
     "dcd_loss_rows_finish": (c_int, [c_void_p, ctypes.POINTER(LossRowsArgs)]),
     "dcd_encode_targets": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_double] * 3 + [c_int, c_int, c_void_p, c_int]),
     "dcd_preprocess_images": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dcd_eval_overlaps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64] + [c_void_p] * 5),
+    "dcd_eval_match": (c_int, [c_void_p, ctypes.POINTER(EvalMatchArgs)]),
+    "dcd_eval_sum_similarity": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

@@ -678,6 +678,61 @@ int dcd_preprocess_images(void *stream, const uint8_t *src, int64_t src_bytes, c
                           int in_h, int in_w, int to_bgr, float *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * KITTI average precision on the device (csrc/eval.hip).  Replaces the two slow loops of the
+ * reference's evaluator, DGDE/data/datasets/evaluation/kitti_object_eval_python: `calculate_iou_partly` (eval.py:338-412) with
+ * its numba.cuda kernel `rotate_iou_kernel_eval` (rotate_iou.py:264-296), and `compute_statistics_jit` (eval.py:155-273) as
+ * `eval_class` drives it.  All images of a split travel together as concatenated arrays with per-image offset tables
+ * (n_img + 1 entries each, first 0): gt_off / dt_off / dc_off int32 count ground-truth, detection and DontCare boxes, pair_off
+ * int64 counts dt_i * gt_i.  G, D, n_dc, P are the totals (the last entries).  Nothing is allocated, copied or synchronised.
+ *
+ * dcd_eval_overlaps: out (3, P) float64; image i's block out[m][pair_off[i] ...] is laid out [dt, gt], the `overlaps[j, i]` of
+ *   compute_statistics_jit.  m = 0: `image_box_overlap` criterion -1 (eval.py:84-111) in float64 on box2d (., 4) x1 y1 x2 y2.
+ *   m = 1: `bev_box_overlap`, m = 2: `d3_box_overlap` (eval.py:114-152) on box3d (., 7) float64 x y z l h w ry (location,
+ *   dimensions in the l h w order of kitti_common.py:325-327, rotation_y).  The rotated intersection area is computed once, in
+ *   float32 on float32-rounded x z l w ry as the reference does (rotate_iou.py:314-315), by clipping the detection against
+ *   the ground-truth box in that box's own frame (never more than 8 vertices; coincident boxes give 1, touching boxes 0,
+ *   where the reference's vertex collection loses points); height overlap, areas and volumes are float64.  P == 0 is
+ *   valid and launches nothing.
+ * dcd_eval_match: one wave per (image, combination).  comb (n_comb, 3) int32: metric 0..2, row of the ignore tables, slot of
+ *   the similarity output or -1 (read by mode DCD_EVAL_MATCH_COUNTS only); min_overlap (n_comb) float64, >= 0.  ign_gt (n_rows, G) / ign_dt (n_rows, D) int8 are the
+ *   0 / 1 / -1 flags of `clean_data` (eval.py:28-81) per (class, difficulty); overlaps is dcd_eval_overlaps' output (or any
+ *   (3, P) float64 of that layout); dc_box (n_dc, 4) the DontCare boxes.  max_dt: the largest detection count of one image,
+ *   at most 4096.
+ *     mode DCD_EVAL_MATCH_SCORES (compute_fp = False, thresh = 0): scores (n_comb, G) float64, fully written: the score of the
+ *       detection assigned to each ground-truth box as a true positive, else -1e7.
+ *     mode DCD_EVAL_MATCH_COUNTS (compute_fp = True): thresholds (n_comb, T) float64 with n_thresh (n_comb) valid entries per
+ *       row, T <= 41.  counts (n_comb, T, 3) int32 tp fp fn, ZEROED BY THE CALLER, summed over images with integer atomics
+ *       (the DontCare stage of eval.py:246-260 included, criterion-0 overlap in float64, metric 0 only).  sim_part
+ *       (n_img, n_slots, T) float64, written for every combination with a slot: the image's AOS similarity sum
+ *       (eval.py:261-270, 0 where the reference returns -1 and past n_thresh).  No floating-point atomics.
+ * dcd_eval_sum_similarity: out[k] = sum_i part[i][k] for part (n_img, n), in image order: bit-identical from run to run.
+ * Status: DCD_ERR_BAD_ARG for a null pointer that is needed, a negative size, T > 41, n_comb > 65535, max_dt > 4096.
+ * ---------------------------------------------------------------------------------------------- */
+#define DCD_EVAL_MATCH_SCORES 0
+#define DCD_EVAL_MATCH_COUNTS 1
+#define DCD_EVAL_MAX_THRESHOLDS 41
+typedef struct {
+    int mode, n_img, n_comb, n_rows, G, D, n_dc, max_dt, T, n_slots;
+    int64_t P;
+    const int32_t *gt_off, *dt_off, *dc_off;
+    const int64_t *pair_off;
+    const double *overlaps;
+    const int8_t *ign_gt, *ign_dt;
+    const double *dt_score, *gt_alpha, *dt_alpha, *dt_box2d, *dc_box;
+    const int32_t *comb;
+    const double *min_overlap, *thresholds;
+    const int32_t *n_thresh;
+    double *scores;
+    int32_t *counts;
+    double *sim_part;
+} dcd_eval_match_args;
+int dcd_eval_overlaps(void *stream, int n_img, const int32_t *gt_off, const int32_t *dt_off, const int64_t *pair_off, int G, int D,
+                      int64_t P, const double *gt_box2d, const double *dt_box2d, const double *gt_box3d, const double *dt_box3d,
+                      double *out);
+int dcd_eval_match(void *stream, const dcd_eval_match_args *args);
+int dcd_eval_sum_similarity(void *stream, const double *part, int n_img, int n, double *out);
+
+/* ------------------------------------------------------------------------------------------------
  * The optimizer end of the train step (csrc/optim.hip): `torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)` followed by
  * `AdamW.step()` (DGDE/engine/trainer.py:144-147; DGDE/solver/__init__.py:10-62: AdamW, betas (0.9, 0.99), one learning rate per
  * parameter) over LISTS of fp32 tensors.  The host arrays of pointers / element counts are read during the call only (they travel
