@@ -84,3 +84,46 @@ def test_example_dconv_shapes(oracle_dcn):
     assert tuple(out.shape) == (2, 8, 16, 16)
     grads = oracle_dcn.dcn_v2_backward(x, w, b, off, m, torch.ones_like(out), 3, 3, 1, 1, 1, 1, 1, 1, 2)
     assert [tuple(g.shape) for g in grads] == [(2, 8, 16, 16), (2, 36, 16, 16), (2, 18, 16, 16), (8, 8, 3, 3), (8,)]
+
+
+def _boundary_case():
+    """The offsets of test_gpu_dcn.py::test_boundary_samples: samples in (-1, 0) and (H - 1, H), on the border and outside."""
+    from test_gpu_dcn import make_case
+    x, w, b, off, m, gy = make_case(1, 4, 4, 6, 7, seed=3)
+    off.zero_()
+    off[:, 0::2] = torch.tensor([-0.5, -1.0, -1.5, 0.25, 6.5, 5.99, -0.999, 5.0, 7.0]).view(1, 9, 1, 1)
+    off[:, 1::2] = torch.tensor([-0.5, -0.25, 7.5, 6.99, -1.0, 0.5, -0.999, 6.0, -2.0]).view(1, 9, 1, 1)
+    return (x, w, b, off, m, gy), 1
+
+
+def _made_case(B, C, Co, H, W, dg, off_scale):
+    from test_gpu_dcn import make_case
+    return make_case(B, C, Co, H, W, dg, off_scale=off_scale, seed=1), dg
+
+
+def test_bf16_reference_without_rounding_is_the_oracle(oracle_dcn):
+    """tests/dcn_bf16_reference.py with r = identity (float64 columns, float64 sums, autograd for everything upstream of the
+    columns) against the C oracle, forward and all five gradients.  Pins the reference's sampling rules (open interval, per-corner
+    bounds, floor, one-sided coordinate derivative, deformable groups) before the GPU tests lean on them.
+    Against the oracle's float64 instantiation: 1e-12 of each tensor's max norm (measured: 2.3e-15 at worst).
+    Against the fp32 oracle the difference is the oracle's own accumulation noise: 1e-6 on the three small cases (measured 3.4e-7 at
+    worst); the two cases that sum 288 / 108 products per output and 9 x 70 per column gradient measure 1.4e-6 (forward, two groups)
+    and 2.0e-6 (grad_mask, 12 -> 70) -- the float64 comparison shows that this is the fp32 oracle, not the reference -- and are
+    held at 3e-6."""
+    from dcn_bf16_reference import dcn_reference
+    names = ("forward", "grad_input", "grad_offset", "grad_mask", "grad_weight", "grad_bias")
+    for ((x, w, b, off, m, gy), dg), bar32 in ((_made_case(2, 5, 4, 7, 9, 1, 3.0), 1e-6), (_made_case(2, 64, 32, 9, 11, 2, 2.0), 3e-6),
+                                               (_made_case(1, 6, 3, 5, 6, 3, 6.0), 1e-6), (_made_case(1, 12, 70, 17, 36, 1, 1.5), 3e-6),
+                                               (_boundary_case(), 1e-6)):
+        a = (3, 3, 1, 1, 1, 1, 1, 1, dg)
+        y, grads = dcn_reference(x, w, b, off, m, gy, dg=dg, rounded=False)
+        for dtype, bar in ((torch.float64, 1e-12), (torch.float32, bar32)):
+            t = [v.to(dtype) for v in (x, w, b, off, m, gy)]
+            ref = (oracle_dcn.dcn_v2_forward(*t[:5], *a),) + tuple(oracle_dcn.dcn_v2_backward(*t, *a))
+            ratios = []
+            for name, got, r_ in zip(names, (y,) + grads, ref):
+                assert got.shape == r_.shape, name
+                ratios.append((got - r_.double()).abs().max().item() / (r_.abs().max().item() + 1e-12))
+            print("reference vs oracle %s %s dg %d: %s" % (dtype, tuple(x.shape), dg, " ".join("%.1e" % v for v in ratios)))
+            for name, ratio in zip(names, ratios):
+                assert ratio <= bar, (name, tuple(x.shape), dg, dtype, ratio)
