@@ -33,6 +33,12 @@ def test_head_rows_equal_one_linear_per_head(cuda, R, K):
     for a, b in zip(got, want):
         assert a.shape == b.shape
         assert (a - b).abs().max().item() <= 5e-6 * max(b.abs().max().item(), 1e-3)
+    # the feature gradient trunk by trunk: trunk 2 feeds 223 outputs, trunk 0 feeds 6 -- one scale over all three judges trunk 2
+    for t in range(T):
+        a, b = got[0][t], want[0][t]
+        ratio = (a - b).abs().max().item() / b.abs().max().item()
+        print("head rows R=%d K=%d: feature gradient of trunk %d, error / maximum %.2e" % (R, K, t, ratio))
+        assert ratio <= 5e-6, (t, ratio)
     # reproducible: fixed summation order in all three kernels
     again = torch.autograd.grad(ops.head_rows(feat, trunk_of, ws, bs), [feat] + ws + bs, gy)
     assert all(torch.equal(a, b) for a, b in zip(got, again))

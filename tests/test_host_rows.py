@@ -63,6 +63,63 @@ def _rows_inputs(empty_image=False, mixed_flags=False, seed=0):
     return loss, tv, pois
 
 
+ORACLE_OPS = ("pairs_kpts_depth", "compute_z", "focal_loss", "giou_loss", "nms_hm", "select_topk", "select_point_of_interest", "iou_3d")
+
+# The noise seed of `_rows_inputs` per variant for the column-by-column gradient checks.  The pair-depth term trains the 1 500
+# key-point pairs with the largest |dv| of the PREDICTED key points: a discrete choice.  With mixed flags and seed 0 the fp32 and
+# the float64 op-by-op rows choose differently (their `valid_l` gradients differ by 7.2e-3 / 3.4e-2 of the extra_kpts_2d / _3d
+# maxima), which says nothing about the arithmetic.  Seeds 0-9 searched on the CPU: 0, 2, 3, 4, 7, 9 flip (1.1e-2 .. 5.7e-2),
+# 1 and 5 agree to 2.1e-6 / 2.4e-6, 6 and 8 agree within 2e-6 in every (column, head) (worst 1.7e-6 / 1.6e-6).  6 is used.
+# Without mixed flags seed 0 agrees to 1.6e-6.
+COLUMN_SEED = {False: 0, True: 6}
+_COLUMN_REFERENCE = {}
+
+
+def column_reference(monkeypatch, empty_image, mixed_flags):
+    """(loss, tv, pois, names, G64): the inputs of one variant and G64 (25, B, M, 415), the float64 autograd gradient of every
+    column sum of the op-by-op rows (`Loss_Computation._rows` on the oracle ops, patched in only while this runs) w.r.t. the
+    head outputs; a column without a gradient path gives zeros.  Computed once per variant; callers must not modify it."""
+    from dcd_amd import ops
+    from oracle import torch_ops
+    key = (empty_image, mixed_flags)
+    if key not in _COLUMN_REFERENCE:
+        loss, tv, pois = _rows_inputs(empty_image, mixed_flags, seed=COLUMN_SEED[mixed_flags])
+        with monkeypatch.context() as mp:
+            for name in ORACLE_OPS:
+                mp.setattr(ops, name, getattr(torch_ops, name))
+            p = pois.double().requires_grad_()
+            S, ix = loss._rows({'reg_pois': p, 'reg': None}, tv)
+            assert S.dtype == torch.float64 and sorted(ix.values()) == list(range(25))
+            G = []
+            for c in range(25):
+                g = torch.autograd.grad(S[c], p, retain_graph=True, allow_unused=True)[0] if S[c].requires_grad else None
+                G.append(torch.zeros_like(p) if g is None else g)
+        _COLUMN_REFERENCE[key] = (loss, tv, pois, {v: k for k, v in ix.items()}, torch.stack(G))
+    return _COLUMN_REFERENCE[key]
+
+
+# columns that are counts, masks or logging metrics: no gradient path in the op-by-op rows, so exactly zero from the kernel
+NO_GRADIENT_COLUMNS = {'ov', 'iou', 'm2', 'depth_real', 'iou3d', 'm2d', 'm3d', 'invalid_l', 'n_valid', 'n_invalid', 'mae', 'kd_log'}
+
+
+def check_column_gradients(got, ref, names, loss, tv, what):
+    """got, ref (25, B, M, 415): every column on every head at 2e-5 of that (column, head)'s own maximum in the reference;
+    exact zeros where the reference has none and in the rows of slots without an object.  Returns the worst ratio."""
+    from grad_scales import assert_close_by_group, head_groups
+    groups = head_groups(loss)
+    assert [b - a for _, a, b in groups] == [4, 2, 20, 3, 3, 8, 8, 1, 1, 146, 219]
+    empty = {names[c] for c in range(25) if not ref[c].any()}
+    # (the fixture's objects are all untruncated with every keypoint depth valid: without mixed flags `trunc` and `kd_i` are empty too)
+    assert NO_GRADIENT_COLUMNS <= empty <= NO_GRADIENT_COLUMNS | {'trunc', 'kd_i'}, sorted(empty ^ NO_GRADIENT_COLUMNS)
+    worst = 0.0
+    for c in range(25):
+        if names[c] in empty:
+            assert not got[c].any(), "%s, column %s: no gradient path, got %.3e" % (what, names[c], got[c].abs().max().item())
+        worst = max(worst, assert_close_by_group(got[c], ref[c], groups, 2e-5, "%s, column %s" % (what, names[c])))
+        assert not got[c][~tv['reg_mask'].bool().cpu()].any(), "%s, column %s: a slot without an object has a gradient" % (what, names[c])
+    return worst
+
+
 def _host_args(loss, tv, pois, keep):
     from dcd_amd import _lib, ops
     enc = loss.anno_encoder
@@ -116,17 +173,19 @@ def _run_host(host_rows, loss, tv, pois, gsums):
     a.cols, a.corners_pred, a.corners_tgt = cols.data_ptr(), corners[0].data_ptr(), corners[1].data_ptr()
     a.iou3d, a.sums = iou3d.data_ptr(), sums.data_ptr()
     host_rows.host_rows_forward(ctypes.byref(a))
-    gs = gsums.contiguous()
-    gpois = torch.full((BM, C), float('nan'), dtype=f32)      # every element must be written
-    gpair = torch.full((BM, NP), float('nan'), dtype=f32)
-    a.grad_sums, a.grad_pois, a.grad_pair = gs.data_ptr(), gpois.data_ptr(), gpair.data_ptr()
-    host_rows.host_rows_backward(ctypes.byref(a))
-    assert torch.isfinite(gpois).all() and torch.isfinite(gpair).all()
-    depth.backward(gpair)
-    gk, gk3 = kp.grad.contiguous(), k3.grad.contiguous()
-    a.grad_kps, a.grad_kps3d = gk.data_ptr(), gk3.data_ptr()
-    host_rows.host_rows_finish(ctypes.byref(a))
-    return sums, gpois.view(B, M, C), corners
+    out = []
+    for gs in (gsums if gsums.dim() == 2 else gsums[None]):   # forward once, the backward for every weighting of the column sums
+        gs = gs.contiguous()
+        gpois = torch.full((BM, C), float('nan'), dtype=f32)      # every element must be written
+        gpair = torch.full((BM, NP), float('nan'), dtype=f32)
+        a.grad_sums, a.grad_pois, a.grad_pair = gs.data_ptr(), gpois.data_ptr(), gpair.data_ptr()
+        host_rows.host_rows_backward(ctypes.byref(a))
+        assert torch.isfinite(gpois).all() and torch.isfinite(gpair).all()
+        gk, gk3 = (g.contiguous() for g in torch.autograd.grad(depth, (kp, k3), gpair, retain_graph=True))
+        a.grad_kps, a.grad_kps3d = gk.data_ptr(), gk3.data_ptr()
+        host_rows.host_rows_finish(ctypes.byref(a))
+        out.append(gpois.view(B, M, C))
+    return sums, (torch.stack(out) if gsums.dim() == 2 else out[0]), corners
 
 
 @pytest.mark.parametrize("empty_image,mixed_flags", [(False, False), (True, False), (False, True)])
@@ -153,6 +212,21 @@ def test_row_kernel_arithmetic_equals_the_op_by_op_rows(cpu_backend, host_rows, 
     err = (gpois - g_ref).abs().max().item()
     assert err <= 2e-5 * scale, (err, scale, np.unravel_index((gpois - g_ref).abs().argmax().item(), tuple(g_ref.shape)))
     assert (gpois[~tv['reg_mask'].bool()] == 0).all()
+
+
+@pytest.mark.parametrize("empty_image,mixed_flags", [(False, False), (True, False), (False, True)])
+def test_row_kernel_gradient_of_every_column_on_every_head(monkeypatch, host_rows, empty_image, mixed_flags):
+    """The hand-written backward column by column (one-hot weights on the 25 column sums) against float64 autograd of the
+    op-by-op rows, every head on its own scale: 2e-5 of the (column, head) maximum.  One scale over the whole gradient (the test
+    above) sees only the dense key-point heads: the 2-D box head's gradient is 4e-5 of theirs.  The fp32 op-by-op rows alone sit
+    at most 1.7e-6 from float64 on this yardstick (COLUMN_SEED), 10x inside the bar.
+    Measured (host build, g++ -O2): worst (column, head) 1.8e-6 plain, 1.4e-6 empty image, 1.7e-6 mixed flags."""
+    loss, tv, pois, names, G64 = column_reference(monkeypatch, empty_image, mixed_flags)
+    if mixed_flags:
+        assert not any(not G64[c].any() for c in range(25) if names[c] in ('trunc', 'kd_i'))
+    _, got, _ = _run_host(host_rows, loss, tv, pois, torch.eye(25))
+    worst = check_column_gradients(got, G64, names, loss, tv, "host build")
+    print("worst (column, head) error / maximum: %.2e" % worst)
 
 
 def test_column_names_are_the_same_in_both_evaluations(cpu_backend):
