@@ -139,7 +139,9 @@ __global__ __launch_bounds__(256) void spd_diag_block(float *__restrict__ A, int
 #ifdef SPD_PROFILE
     tc[2] = clock64();
 #endif
-    if (tid == 0 && bad_flag && info) atomicMax(info + b, k0 + 1);      // not positive definite (or NaN) somewhere in this block
+    // not positive definite (or NaN) somewhere in this block.  The FIRST such block is reported: its NaN factor spreads through the
+    // trailing update, so every later block of the matrix is bad as well (a maximum would always name the last block).
+    if (tid == 0 && bad_flag && info) atomicCAS(info + b, 0, k0 + 1);
     for (int e = tid; e < SP_NB * SP_NB; e += 256) {
         const int row = e >> 7, col = e & 127;
         if (row < nb && col <= row) Ab[(size_t)row * n + col] = Ls[row * SP_LS + col];

@@ -350,9 +350,10 @@ int dcd_sgemm_shifted(void *stream, const float *A, int lda, long long strideA, 
  *     C[z] (M x N, row-major, ldc) = alpha * A[z] B[z]  (+ C[z] when accumulate)
  *     A(m,k) = a_kcontig ? A[m*lda + k] : A[k*lda + m]        B(k,n) = b_kcontig ? B[n*ldb + k] : B[k*ldb + n]
  * lower_only: tiles entirely above the diagonal are skipped (symmetric results; entries above the diagonal of the remaining
- * tiles are still written).  All pointers 16-byte aligned, lda / ldb / strides multiples of 4.  Used for the Schur complement
- * S = diag(c) - G^T diag(1/r) G of the transport layer's backward (GMW/lib/optimal_transport.py:93-100), written straight into
- * the buffer dcd_spd_solve factorises. */
+ * tiles are still written).  A and B 16-byte aligned, lda / ldb / strideA / strideB multiples of 4; C, ldc and strideC need only
+ * the alignment of a float.  Elements of C outside the M x N region and in skipped tiles are not touched.  Used for the Schur
+ * complement S = diag(c) - G^T diag(1/r) G of the transport layer's backward (GMW/lib/optimal_transport.py:93-100), written
+ * straight into the buffer dcd_spd_solve factorises. */
 int dcd_sgemm(void *stream, const float *A, int lda, long long strideA, int a_kcontig, const float *B, int ldb, long long strideB,
               int b_kcontig, float *C, int ldc, long long strideC, int M, int N, int K, int Z, float alpha, int accumulate,
               int lower_only);

@@ -12,6 +12,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from make_golden_gmw import inputs  # noqa: E402  (seeded input builder shared with the generator; pure numpy)
+import transport_refs as R  # noqa: E402  (references and bounds of the transport layer's device backward)
 
 
 def _run(device, compute_z):
@@ -110,6 +111,46 @@ def test_transport_backward_equals_generic_declarative_formula():
             DP = Hinv @ A.T @ torch.linalg.inv(A @ Hinv @ A.T) @ A @ Hinv - Hinv
             ref = v[k].double() @ DP
             assert (got[k].double() - ref).abs().max().item() <= tol * ref.abs().max().item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", R.TRANSPORT_SHAPES)
+def test_transport_backward_on_the_device_matches_float64_by_element(cuda, monkeypatch, shape):
+    """`gradient` on the device route (ops.schur_lower -> dcd_sgemm, ops.spd_solve_inplace -> dcd_spd_solve) against `gradient` in
+    float64 on the host, from the same fp32 plan: max|got - ref| <= 4e-7 cond(S) max|ref|, the solver's own bound, cond(S) the
+    largest of the batch in float64.  m != n puts the tail of the contraction (K = m - 1) and of the tiles in different places;
+    n = 4 is below one panel, 132 / 260 / 516 leave a 4-wide last block, 384 is whole blocks.  Each wrapper runs exactly once.
+
+    error / max|ref| (generator seeded 11; host = the fp32 LAPACK branch on the CPU, device = MI355X):
+        (b, m, n)       cond(S)   host fp32   device    bound
+        (2, 5, 4)          22     1.7e-6      8.7e-7    8.8e-6
+        (3, 100, 132)     105     5.8e-7      4.6e-7    4.2e-5
+        (2, 260, 260)     265     5.4e-7      1.1e-6    1.1e-4
+        (1, 385, 384)     389     1.0e-6      9.2e-7    1.6e-4
+        (2, 131, 516)     136     1.3e-7      3.2e-7    5.4e-5
+    """
+    from dcd_amd import ops
+    from dcd_amd.gmw.optimal_transport import RegularisedTransportFn as T
+    calls = {"schur_lower": 0, "spd_solve_inplace": 0}
+
+    def spy(name):
+        inner = getattr(ops, name)
+
+        def counted(*args, **kwargs):
+            calls[name] += 1
+            return inner(*args, **kwargs)
+        monkeypatch.setattr(ops, name, counted)
+    spy("schur_lower")
+    spy("spd_solve_inplace")
+    monkeypatch.delenv("DCD_GMW_SOLVER", raising=False)
+    tp = R.transport_problem(*shape)
+    got = T.gradient(tp.P32.to(cuda), R.LMBDA, tp.v.float().to(cuda)).cpu().double()
+    assert calls == {"schur_lower": 1, "spd_solve_inplace": 1}, calls
+    d = (got - tp.ref).abs()
+    err = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d).max().item()
+    print("transport backward %s: cond(S) %.0f, device error / max|ref| %.2e, bound %.2e" % (
+        shape, tp.cond, err / tp.ref.abs().max().item(), 4e-7 * tp.cond))
+    assert err <= R.solver_bound(tp.cond, tp.ref), (err / tp.ref.abs().max().item(), tp.cond)
 
 
 @pytest.mark.gpu
