@@ -699,8 +699,10 @@ __device__ __forceinline__ float wave_sum64(float v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void context_norm_fwd(const float *__restrict__ x, float *__restrict__ y, float *__restrict__ inv_out,
-                                                        int rows, int K, float eps)
+// RELU_ADD: the inference form of a residual block's tail, y = relu(context_norm(x)) + residual, no `inv` (there is no backward).
+template <bool RELU_ADD>
+__global__ __launch_bounds__(256) void context_norm_fwd(const float *__restrict__ x, const float *__restrict__ residual,
+                                                        float *__restrict__ y, float *__restrict__ inv_out, int rows, int K, float eps)
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -713,8 +715,13 @@ __global__ __launch_bounds__(256) void context_norm_fwd(const float *__restrict_
     const float var = wave_sum64(q) / (float)(K - 1);
     const float inv = 1.f / sqrtf(var + eps);
     float *yr = y + (size_t)row * K;
-    for (int i = lane; i < K; i += 64) yr[i] = (xr[i] - m) * inv;
-    if (lane == 0) inv_out[row] = inv;
+    if constexpr (RELU_ADD) {
+        const float *rr = residual + (size_t)row * K;
+        for (int i = lane; i < K; i += 64) yr[i] = fmaxf((xr[i] - m) * inv, 0.f) + rr[i];
+    } else {
+        for (int i = lane; i < K; i += 64) yr[i] = (xr[i] - m) * inv;
+        if (lane == 0) inv_out[row] = inv;
+    }
 }
 
 __global__ __launch_bounds__(256) void context_norm_bwd(const float *__restrict__ dy, const float *__restrict__ y,
@@ -743,8 +750,9 @@ __device__ __forceinline__ float block_sum256(float v, float *sh)
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-__global__ __launch_bounds__(256) void context_norm_fwd_row(const float *__restrict__ x, float *__restrict__ y, float *__restrict__ inv_out,
-                                                            int K, float eps)
+template <bool RELU_ADD>
+__global__ __launch_bounds__(256) void context_norm_fwd_row(const float *__restrict__ x, const float *__restrict__ residual,
+                                                            float *__restrict__ y, float *__restrict__ inv_out, int K, float eps)
 {
     __shared__ float sh[4];
     const int row = blockIdx.x, K4 = K >> 2;
@@ -770,9 +778,17 @@ __global__ __launch_bounds__(256) void context_norm_fwd_row(const float *__restr
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int i = threadIdx.x + 256 * j;
-        if (i < K4) yr[i] = make_float4(v[j].x * inv, v[j].y * inv, v[j].z * inv, v[j].w * inv);
+        if (i >= K4) continue;
+        if constexpr (RELU_ADD) {
+            const float4 r = reinterpret_cast<const float4 *>(residual + (size_t)row * K)[i];
+            yr[i] = make_float4(fmaxf(v[j].x * inv, 0.f) + r.x, fmaxf(v[j].y * inv, 0.f) + r.y, fmaxf(v[j].z * inv, 0.f) + r.z,
+                                fmaxf(v[j].w * inv, 0.f) + r.w);
+        } else {
+            yr[i] = make_float4(v[j].x * inv, v[j].y * inv, v[j].z * inv, v[j].w * inv);
+        }
     }
-    if (threadIdx.x == 0) inv_out[row] = inv;
+    if constexpr (!RELU_ADD)
+        if (threadIdx.x == 0) inv_out[row] = inv;
 }
 
 __global__ __launch_bounds__(256) void context_norm_bwd_row(const float *__restrict__ dy, const float *__restrict__ y,
@@ -1098,9 +1114,22 @@ int dcd_context_norm_forward(void *stream_, const float *x, float *y, float *inv
     if (rows == 0) return DCD_OK;
     if (!x || !y || !inv || rows < 0 || K < 2) return DCD_ERR_BAD_ARG;
     if ((K & 3) == 0 && K <= 4096 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
-        hipLaunchKernelGGL(context_norm_fwd_row, dim3(rows), dim3(256), 0, stream, x, y, inv, K, eps);
+        hipLaunchKernelGGL(context_norm_fwd_row<false>, dim3(rows), dim3(256), 0, stream, x, nullptr, y, inv, K, eps);
     else
-        hipLaunchKernelGGL(context_norm_fwd, dim3((rows + 3) / 4), dim3(256), 0, stream, x, y, inv, rows, K, eps);
+        hipLaunchKernelGGL(context_norm_fwd<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, nullptr, y, inv, rows, K, eps);
+    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+}
+
+int dcd_context_norm_relu_add_forward(void *stream_, const float *x, const float *residual, float *y, int rows, int K, float eps)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    if (rows == 0) return DCD_OK;
+    if (!x || !residual || !y || rows < 0 || K < 2) return DCD_ERR_BAD_ARG;
+    if ((K & 3) == 0 && K <= 4096 && (((uintptr_t)x | (uintptr_t)residual | (uintptr_t)y) & 15) == 0)
+        hipLaunchKernelGGL(context_norm_fwd_row<true>, dim3(rows), dim3(256), 0, stream, x, residual, y, nullptr, K, eps);
+    else
+        hipLaunchKernelGGL(context_norm_fwd<true>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, residual, y, nullptr, rows, K, eps);
     return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
 }
 

@@ -1572,6 +1572,50 @@ def context_norm(x, eps=1e-3):
     return _ContextNorm.apply(x, eps)
 
 
+def _require_no_grad(what, *tensors):
+    for t in tensors:
+        if t.requires_grad:
+            raise _lib.DcdHipError("%s has no backward: call it under torch.no_grad() on detached tensors" % what)
+
+
+def context_norm_relu_add(x, residual, eps=1e-3):
+    """`relu(context_norm(x)) + residual`, the tail of a residual block of GMW's extractor at inference, in one launch."""
+    _lib.require_cuda(x, residual)
+    _require_no_grad("context_norm_relu_add", x, residual)
+    if x.shape != residual.shape:
+        raise ValueError("context_norm_relu_add: x %s and residual %s differ in shape" % (tuple(x.shape), tuple(residual.shape)))
+    x, residual = _f32c(x), _f32c(residual)
+    K = x.shape[-1]
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().dcd_context_norm_relu_add_forward(_lib.stream_of(x), x.data_ptr(), residual.data_ptr(), y.data_ptr(),
+                                                            x.numel() // K if K else 0, K, float(eps)), "dcd_context_norm_relu_add_forward")
+    return y
+
+
+def gmw_refine(f4, f6, depths, good_idx, raw_location, dim):
+    """GMW's refinement after the extractors (GMW/main.py:524-548): f4, f6 (B, C, K) features, depths (B, K) and good_idx
+    (B, num_k) of `compute_z`, raw_location / dim (B, 3) -> (weights (B, K), pred_depth (B), pred_location (B, 3))."""
+    _lib.require_cuda(f4, f6, depths, good_idx, raw_location, dim)
+    _require_no_grad("gmw_refine", f4, f6, depths, raw_location, dim)
+    if f4.dim() != 3 or f4.shape != f6.shape:
+        raise ValueError("gmw_refine: f4 %s and f6 %s must both be (B, C, K)" % (tuple(f4.shape), tuple(f6.shape)))
+    B, C, K = f4.shape
+    if depths.shape != (B, K) or good_idx.dim() != 2 or good_idx.shape[0] != B or raw_location.shape != (B, 3) or dim.shape != (B, 3):
+        raise ValueError("gmw_refine: depths (B, K), good_idx (B, num_k), raw_location (B, 3), dim (B, 3) expected")
+    f4, f6, depths, raw_location, dim = (_f32c(t) for t in (f4, f6, depths, raw_location, dim))
+    good_idx = good_idx.long().contiguous()
+    weights = torch.empty((B, K), dtype=torch.float32, device=f4.device)
+    pred_depth = torch.empty((B,), dtype=torch.float32, device=f4.device)
+    pred_location = torch.empty((B, 3), dtype=torch.float32, device=f4.device)
+    if B == 0:
+        return weights, pred_depth, pred_location
+    st = _lib.lib().dcd_gmw_refine(_lib.stream_of(f4), f4.data_ptr(), f6.data_ptr(), depths.data_ptr(), good_idx.data_ptr(),
+                                   good_idx.shape[1], raw_location.data_ptr(), dim.data_ptr(), B, C, K, weights.data_ptr(),
+                                   pred_depth.data_ptr(), pred_location.data_ptr())
+    _lib.check(st, "dcd_gmw_refine")
+    return weights, pred_depth, pred_location
+
+
 class _FanOut(torch.autograd.Function):
     """n aliases of one tensor whose gradients are summed by ONE kernel (autograd would run n-1 pairwise additions, each
     a read-read-write pass over the map)."""

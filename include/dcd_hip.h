@@ -374,6 +374,24 @@ int dcd_spd_solve(void *stream, float *S, float *y, int batch, int n, int rows, 
 int dcd_context_norm_forward(void *stream, const float *x, float *y, float *inv, int rows, int K, float eps);
 int dcd_context_norm_backward(void *stream, const float *grad_y, const float *y, const float *inv, float *grad_x, int rows, int K);
 
+/* The tail of a residual block of that extractor at inference (conv1d_resnet_block, yi2018cvpr/ops.py:67-131: gcn -> ReLU -> + input)
+ * in one pass: y = relu(context_norm(x)) + residual, x / residual / y (rows, K).  No `inv`, no backward: for torch.no_grad() only. */
+int dcd_context_norm_relu_add_forward(void *stream, const float *x, const float *residual, float *y, int rows, int K, float eps);
+
+/* GMW inference (GMW/main.py:524-548 `validate` after the extractors; GMW/model/model.py:154-199): edge weights, weighted depth and
+ * the refined location of B objects without the K x K distance matrix (csrc/gmw.hip).
+ *   f4, f6: (B, C, K) the two extractors' outputs as they lie (points contiguous).  depths: (B, K) edge depths of `compute_z`.
+ *   good_idx: (B, num_k) int64 indices into K, as `compute_z` returns them.  raw_location, dim: (B, 3) each, dim = (h, w, l).
+ *   weights (B, K) = 1 / d_k with d_k = sqrt(max(sum_c (f4_c / n4 - f6_c / n6)^2, 1e-30)), n = max(L2 norm over C, 1e-12): the
+ *     diagonal of `pairwise_l2_dist` of the normalised features, in the difference form (the expanded one cancels for small d).
+ *   pred_depth (B) = sum softmax(weights[good_idx]) * depths[good_idx]; pred_location (B, 3): y -= h/2, scale by pred_depth / z,
+ *     y += h/2.  An index outside [0, K) makes that object's pred_depth and pred_location NaN.
+ * Sums run in a fixed order; an object's result does not depend on B or on its place in the batch.
+ * Status: DCD_ERR_BAD_ARG for a null pointer, B / C / K / num_k < 1 or num_k > K. */
+int dcd_gmw_refine(void *stream, const float *f4, const float *f6, const float *depths, const long long *good_idx, int num_k,
+                   const float *raw_location, const float *dim, int B, int C, int K, float *weights, float *pred_depth,
+                   float *pred_location);
+
 /* ------------------------------------------------------------------------------------------------
  * Batch normalisation fused with the residual add and ReLU that follow it.  Replaces the stock-op chains
  *   bn -> relu            DGDE/model/backbone/dla_dcn.py:91-93 (BasicBlock), :272-283 (conv levels), :403-410
