@@ -156,6 +156,7 @@ SIGNATURES = {
     "dcd_eval_overlaps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64] + [c_void_p] * 5),
     "dcd_eval_match": (c_int, [c_void_p, ctypes.POINTER(EvalMatchArgs)]),
     "dcd_eval_sum_similarity": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "dcd_gather_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

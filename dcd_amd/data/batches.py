@@ -1,0 +1,139 @@
+"""Batch sources of a training run, and the prefetcher that runs one a batch ahead of the step.
+
+Two sources share one interface -- `source.batch_size`, `len(source)` (images) and `source.get(k) -> (images, targets)`:
+
+    ResidentBatches(split, batch_size, seed, rank=0, world_size=1, is_train=True)       a `ResidentSplit` in device memory
+    StreamingBatches(files, pipeline, batch_size, seed, rank=0, world_size=1, workers=None)
+                                                 PNG decode in a thread pool -> `DeviceInputPipeline` with explicit `flip=`;
+                                                 for a split that does not fit in device memory, and the plain path
+
+Batch k is a PURE FUNCTION of (seed, rank, world_size, k) for both: its images are positions [k B, (k + 1) B) of the rank's
+`TrainingSampler` stream, its flip flags are draws [k B, (k + 1) B) of one `random.Random` stream seeded from (seed, rank), each
+`random() < INPUT.AUG_PARAMS[0][0]` as `DeviceInputPipeline.draw_flips` draws them; an evaluation source walks the images in
+order and never flips.  So `get(k)` after a restart gives the batch an uninterrupted run would have had at iteration k.  (The
+reference restarts its sampler on resume, DGDE/data/samplers/distributed_sampler.py:43-54: a resumed run there sees the first
+images of epoch 0 again.  The difference is deliberate.)  Asking for the batches in order costs nothing extra: the position in
+both streams is kept, and only a jump regenerates them from the seed.
+
+`Prefetcher(source, device, depth=1)` computes batch k + 1 on a side stream when batch k is handed over, so its copy and
+kernels run while the step consumes batch k.  Before a batch is handed over the consuming stream waits for the side stream's
+work on it, and every tensor handed over -- the images and every tensor field of every target -- is `record_stream`'d on the
+consuming stream: the caching allocator would otherwise give their memory back to the side stream's pool, for the batch after
+next to overwrite, while the step still reads it."""
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import torch
+
+from dcd_amd.data.resident import default_workers
+from dcd_amd.data.samplers import TrainingSampler
+
+
+class _Plan:
+    """Indices and flip flags of batch k; sequential requests continue the two streams, a jump regenerates them."""
+
+    def __init__(self, size, batch_size, seed, rank, world_size, flip_p):
+        if batch_size < 1:
+            raise ValueError("batch size %d" % batch_size)
+        self.size, self.batch_size, self.seed, self.rank = int(size), int(batch_size), int(seed), int(rank)
+        self.flip_p = flip_p                                          # None: an evaluation source
+        self.sampler = TrainingSampler(size, shuffle=flip_p is not None, seed=seed, rank=rank, world_size=world_size)
+        self._next = None                                             # the batch number both streams stand at
+
+    def __call__(self, k):
+        B = self.batch_size
+        if k < 0:
+            raise ValueError("batch %d" % k)
+        if self._next != k:
+            self._indices = self.sampler.indices(k * B)
+            self._rng = random.Random(self.seed * 1000003 + self.rank)
+            for _ in range(k * B):
+                self._rng.random()
+        indices = [next(self._indices) for _ in range(B)]
+        draws = [self._rng.random() for _ in range(B)]
+        self._next = k + 1
+        flips = [False] * B if self.flip_p is None else [d < self.flip_p for d in draws]
+        return indices, flips
+
+
+class ResidentBatches:
+    def __init__(self, split, batch_size, seed, rank=0, world_size=1, is_train=True):
+        self.split, self.batch_size, self.is_train = split, int(batch_size), is_train
+        flip_p = float(split.cfg.INPUT.AUG_PARAMS[0][0]) if is_train else None
+        self.plan = _Plan(len(split), batch_size, seed, rank, world_size, flip_p)
+
+    def __len__(self):
+        return len(self.split)
+
+    def get(self, k):
+        indices, flips = self.plan(k)
+        return self.split.batch(indices, flips, img_ids=[self.split.files.img_id(i) for i in indices])
+
+
+class StreamingBatches:
+    def __init__(self, files, pipeline, batch_size, seed, rank=0, world_size=1, workers=None):
+        self.files, self.pipeline, self.batch_size = files, pipeline, int(batch_size)
+        self.is_train = pipeline.is_train
+        self.plan = _Plan(len(files), batch_size, seed, rank, world_size, pipeline.flip_p if pipeline.is_train else None)
+        self._pool = ThreadPoolExecutor(max_workers=default_workers(workers))
+
+    def __len__(self):
+        return len(self.files)
+
+    def _read(self, i):
+        return self.files.frame(i), self.files.sample(i)
+
+    def get(self, k):
+        indices, flips = self.plan(k)
+        read = list(self._pool.map(self._read, indices))
+        return self.pipeline([f for f, _ in read], [s for _, s in read], img_ids=[self.files.img_id(i) for i in indices], flip=flips)
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+
+
+def batch_tensors(images, targets):
+    """Every device tensor of a batch: the images and each tensor field of each target."""
+    out = [images]
+    for t in targets:
+        for name in t.fields():
+            v = t.get_field(name)
+            if torch.is_tensor(v) and v.is_cuda:
+                out.append(v)
+    return out
+
+
+class Prefetcher:
+    def __init__(self, source, device, depth=1):
+        if depth < 1:
+            raise ValueError("depth %d" % depth)
+        self.source, self.device, self.depth = source, torch.device(device), int(depth)
+        self.batch_size = source.batch_size
+        self.side = torch.cuda.Stream(device=self.device)
+        self._ready = {}                                              # k -> (batch, event recorded on the side stream after it)
+
+    def __len__(self):
+        return len(self.source)
+
+    def _produce(self, k):
+        with torch.cuda.stream(self.side):
+            batch = self.source.get(k)
+            event = torch.cuda.Event()
+            event.record(self.side)
+        self._ready[k] = (batch, event)
+
+    def get(self, k):
+        if k not in self._ready:                                      # not the one prefetched: simply compute it
+            self._ready.clear()
+            self._produce(k)
+        batch, event = self._ready.pop(k)
+        for stale in [j for j in self._ready if j < k]:
+            del self._ready[stale]
+        consumer = torch.cuda.current_stream(self.device)
+        consumer.wait_event(event)
+        for t in batch_tensors(*batch):
+            t.record_stream(consumer)
+        for j in range(k + 1, k + 1 + self.depth):
+            if j not in self._ready:
+                self._produce(j)
+        return batch

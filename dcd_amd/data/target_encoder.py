@@ -56,9 +56,7 @@ def pack_raw(samples, max_objs, n_extra):
     return objs, kpts, P, size, count
 
 
-def encode_targets(samples, cfg, device, img_ids=None):
-    """Raw label values of a batch -> [ParamsList] with every training field (kitti.py:572-606), computed on `device`."""
-    device = torch.device(device)
+def _require_supported(cfg, device):
     if device.type != "cuda":
         raise _lib.DcdHipError("dcd_amd.data.target_encoder runs on the GPU only; there is no CPU path")
     ok = (cfg.INPUT.HEATMAP_CENTER == '3D' and cfg.INPUT.ORIENTATION == 'multi-bin' and cfg.INPUT.ORIENTATION_BIN_SIZE == 4
@@ -66,13 +64,36 @@ def encode_targets(samples, cfg, device, img_ids=None):
           and cfg.INPUT.APPROX_3D_CENTER == 'intersect' and cfg.DATASETS.FILTER_ANNO_ENABLE)
     if not ok:
         raise NotImplementedError("the device encoder implements the DGDE.yaml configuration of the target encoding")
+
+
+def encode_targets(samples, cfg, device, img_ids=None):
+    """Raw label values of a batch -> [ParamsList] with every training field (kitti.py:572-606), computed on `device`."""
+    device = torch.device(device)
+    _require_supported(cfg, device)
+    packed = pack_raw(samples, cfg.DATASETS.MAX_OBJECTS, cfg.MODEL.HEAD.EXTRA_KPTS_NUM)
+    dev_in = [torch.from_numpy(a).pin_memory().to(device, non_blocking=True) for a in packed]
+    return encode_packed(dev_in, [s["P"] for s in samples], cfg, device, img_ids)
+
+
+def encode_packed(dev_arrays, P_host_list, cfg, device, img_ids=None):
+    """The device half of `encode_targets`: the five arrays of `pack_raw` ALREADY ON `device` (objs (B,M,16) f64, kpts3d
+    (B,M,n_extra,3) f64, P (B,3,4) f64, size (B,2) i32, count (B) i32, each contiguous) -> [ParamsList].  `P_host_list` holds the
+    same B calibration matrices on the host, for the targets' `Calibration` objects.  A caller whose label arrays stay on the
+    device (dcd_amd/data/resident.py) comes in here; the launch and everything after it are shared with `encode_targets`."""
+    device = torch.device(device)
+    _require_supported(cfg, device)
     M, n_extra = cfg.DATASETS.MAX_OBJECTS, cfg.MODEL.HEAD.EXTRA_KPTS_NUM
     in_w, in_h, down = cfg.INPUT.WIDTH_TRAIN, cfg.INPUT.HEIGHT_TRAIN, cfg.MODEL.BACKBONE.DOWN_RATIO
     n_cls = cfg.DATASETS.MAX_CLASSES_NUM
-    B, K = len(samples), n_extra + 10
+    B, K = len(P_host_list), n_extra + 10
     fw, fh = in_w // down, in_h // down
-    packed = pack_raw(samples, M, n_extra)
-    dev_in = [torch.from_numpy(a).pin_memory().to(device, non_blocking=True) for a in packed]
+    dev_in = list(dev_arrays)
+    shapes = ((B, M, 16), (B, M, n_extra, 3), (B, 3, 4), (B, 2), (B,))
+    dtypes = (torch.float64, torch.float64, torch.float64, torch.int32, torch.int32)
+    for t, shape, dtype in zip(dev_in, shapes, dtypes):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("encode_packed: expected a contiguous %s %s tensor on the device, got %s %s on %s"
+                             % (dtype, shape, t.dtype, tuple(t.shape), t.device))
     out = {}
     for name, tail, dtype in _OUTPUTS:
         shape = (B, n_cls, fh, fw) if tail is None else (B, M) + tuple(K if d == "K" else d for d in tail)
@@ -90,13 +111,13 @@ def encode_targets(samples, cfg, device, img_ids=None):
     out["find_pcl"] = out["find_pcl"].bool()
     ori_mask = torch.ones((B, M), dtype=torch.bool, device=device)
     targets = []
-    for b, s in enumerate(samples):
+    for b, P in enumerate(P_host_list):
         t = ParamsList(image_size=(in_w, in_h), is_train=True)        # the padded size, like the reference (kitti.py:572)
         for name in order[:-3]:
             t.add_field(name, out[name][b])
         t.add_field("ori_mask", ori_mask[b])
         t.add_field("pad_size", out["pad_size"][b])
-        t.add_field("calib", Calibration(np.asarray(s["P"], np.float64)))
+        t.add_field("calib", Calibration(np.asarray(P, np.float64)))
         t.add_field("edge_indices", out["edge_indices"][b])
         t.add_field("edge_len", out["edge_len"][b])
         t.add_field("final_output_w", torch.tensor(fw))

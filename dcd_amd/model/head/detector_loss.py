@@ -646,6 +646,11 @@ class LazyLogDict(dict):
                 if v != v or v in (float('inf'), float('-inf')):
                     raise FloatingPointError("non-finite loss %s: %s" % (k, dict(self)))
 
+    def unread(self):
+        """(names, the packed device tensor, loss keys) while nobody has read the dict, else None: a caller that keeps the values
+        on the device (engine.train's log ring) takes them from here without the synchronisation a read would cost."""
+        return None if self._packed is None else (self._names, self._packed, self._loss_keys)
+
     def __getitem__(self, k):
         self._fill()
         return super().__getitem__(k)

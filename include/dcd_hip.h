@@ -773,6 +773,22 @@ int dcd_adamw_apply(void *stream, int ntensors, void *const *params, void *const
                     void *const *steps, const int64_t *numel, const float *lr, double beta1, double beta2, double eps, double weight_decay,
                     const float *scal);
 
+/* ------------------------------------------------------------------------------------------------
+ * One batch out of tables that stay on the device (csrc/resident.hip; dcd_amd/data/resident.py keeps a decoded KITTI split
+ * there: the image kernel's records, the raw label values of `dcd_encode_targets`, one row per (image, flip)).  For every
+ * table t < n_tables (1 .. 8) and every b < B (1 .. 65535): row b of dst[t] = row index[b] of src[t], rows of row_bytes[t] bytes,
+ * all tables in ONE launch.
+ *   src, dst   HOST arrays of n_tables device pointers, each 4-byte aligned; src[t] holds src_rows[t] rows, dst[t] B rows
+ *   row_bytes  HOST array, each > 0 and a multiple of 4;  src_rows  HOST array, each >= 0
+ *   index      (B) int32 ON THE DEVICE.  An index outside [0, src_rows[t]) gives a zero row in table t: nothing outside src is
+ *              ever read, nothing outside dst[t][0 : B * row_bytes[t]] is ever written.
+ * The host arrays are read during the call only (they travel in the kernel arguments), so the call needs no copy and may be
+ * captured in a graph: a replay follows what `index` holds at that time.  16-byte accesses for a table whose row_bytes is a
+ * multiple of 16 and whose two bases are 16-byte aligned, 4-byte accesses otherwise; same results.  No workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_gather_rows(void *stream, int n_tables, const void *const *src, void *const *dst, const int64_t *row_bytes,
+                    const int64_t *src_rows, const int32_t *index, int B);
+
 #ifdef __cplusplus
 }
 #endif
