@@ -157,6 +157,8 @@ SIGNATURES = {
     "dcd_eval_match": (c_int, [c_void_p, ctypes.POINTER(EvalMatchArgs)]),
     "dcd_eval_sum_similarity": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dcd_gather_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "dcd_sinkhorn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcd_sinkhorn": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_size_t]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

@@ -92,11 +92,11 @@ class FeatureExtractor(nn.Module):
 
 
 class GMW(nn.Module):
-    def __init__(self, num_kpts=73, sinkhorn_lambda=10.0, sinkhorn_tolerance=1e-9):
+    def __init__(self, num_kpts=73, sinkhorn_lambda=10.0, sinkhorn_tolerance=1e-9, device_sinkhorn=False):
         super().__init__()
         self.FeatureExtractor4d = FeatureExtractor(4)
         self.FeatureExtractor6d = FeatureExtractor(6)
-        self.sinkhorn = RegularisedTransport(sinkhorn_lambda, sinkhorn_tolerance)
+        self.sinkhorn = RegularisedTransport(sinkhorn_lambda, sinkhorn_tolerance, device_sinkhorn=device_sinkhorn)
         self.num_kpts = num_kpts
         iu = torch.triu_indices(num_kpts, num_kpts, offset=1)       # row-major upper triangle = masked_select order
         self.register_buffer("pair_i", iu[0], persistent=False)
@@ -135,7 +135,7 @@ class GMW(nn.Module):
         b, m, n = M.size()
         r = M.new_ones((b, m)) / m
         c = M.new_ones((b, n)) / n
-        return self.sinkhorn(M, r, c), diag_feat
+        return self.sinkhorn(M, r, c, positive_marginals=True), diag_feat      # r, c are uniform: nothing to check
 
     def forward(self, kpts_2d, kpts_3d, pred_rot=None, args=None):
         """(B,73,2) K-normalised keypoints, (B,73,3) object-frame keypoints -> (reg_weights (B,2628), edge_P (B,2628,2628))."""

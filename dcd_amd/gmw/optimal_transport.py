@@ -87,9 +87,17 @@ class RegularisedTransportFn(torch.autograd.Function):
             return (field * lamP - w).flatten(start_dim=-2)
 
     @staticmethod
-    def forward(ctx, M, r, c, lmbda, tolerance, max_iterations):
-        P = RegularisedTransportFn.sinkhorn(M.detach(), r.detach(), c.detach(), lmbda, tolerance, max_iterations)
+    def forward(ctx, M, r, c, lmbda, tolerance, max_iterations, device_sinkhorn=False):
         ctx.lmbda = lmbda
+        if device_sinkhorn and M.is_cuda and M.dtype == torch.float32:
+            # csrc/transport.hip: the same iteration stopped by a flag on the device -- no host read per iteration, K built in the
+            # plan's own buffer.  The tensor the kernel returns is what the backward reads; autograd's version counter guards it
+            # against in-place use, so there is no clone.
+            from dcd_amd import ops
+            P, _ = ops.sinkhorn(M.detach(), r.detach(), c.detach(), lmbda, tolerance, max_iterations)
+            ctx.save_for_backward(P)
+            return P
+        P = RegularisedTransportFn.sinkhorn(M.detach(), r.detach(), c.detach(), lmbda, tolerance, max_iterations)
         ctx.save_for_backward(P)
         return P.clone()
 
@@ -100,15 +108,21 @@ class RegularisedTransportFn(torch.autograd.Function):
         grad_input = None
         if ctx.needs_input_grad[0]:
             grad_input = RegularisedTransportFn.gradient(P, ctx.lmbda, grad_output.flatten(start_dim=-2)).reshape(P.size())
-        return grad_input, None, None, None, None, None
+        return grad_input, None, None, None, None, None, None
 
 
 class RegularisedTransport(torch.nn.Module):
-    def __init__(self, lmbda=10.0, tolerance=1e-9, max_iterations=100):
+    """`device_sinkhorn=True`: an fp32 M on the GPU takes the forward of csrc/transport.hip (the backward is the same).
+    `positive_marginals=True` is the caller's word that r, c > 0 -- `GMW.graph_matching` builds uniform ones itself -- and skips
+    the check, which reads the device twice; it is honoured on the device route only."""
+
+    def __init__(self, lmbda=10.0, tolerance=1e-9, max_iterations=100, device_sinkhorn=False):
         super().__init__()
         self.lmbda, self.tolerance, self.max_iterations = lmbda, tolerance, max_iterations
+        self.device_sinkhorn = bool(device_sinkhorn)
 
-    def forward(self, M, r, c):
-        if not (bool((r > 0).all()) and bool((c > 0).all())):
+    def forward(self, M, r, c, positive_marginals=False):
+        device = self.device_sinkhorn and M.is_cuda and M.dtype == torch.float32
+        if not (device and positive_marginals) and not (bool((r > 0).all()) and bool((c > 0).all())):
             raise NotImplementedError("zero prior probabilities (optimal_transport.py:186-216) are not used by GMW and not built")
-        return RegularisedTransportFn.apply(M, r, c, self.lmbda, self.tolerance, self.max_iterations)
+        return RegularisedTransportFn.apply(M, r, c, self.lmbda, self.tolerance, self.max_iterations, device)

@@ -719,6 +719,28 @@ def schur_lower(G, inv_rows, cols, out):
     return out
 
 
+def sinkhorn(M, r, c, lmbda=10.0, tolerance=1e-9, max_iterations=100, max_distance=5.0):
+    """The transport plan of `RegularisedTransportFn.sinkhorn` for M (b, m, n), r (b, m), c (b, n) fp32 on the device, without a
+    host read: csrc/transport.hip stops on a device flag.  Returns (P, iterations) -- the plan in a fresh tensor and a 0-dim int32
+    device tensor holding the number of updates of the row scaling that ran (reading it is the caller's synchronisation)."""
+    _lib.require_cuda(M, r, c)
+    if M.dim() != 3 or M.dtype != torch.float32 or r.dtype != torch.float32 or c.dtype != torch.float32:
+        raise RuntimeError("sinkhorn: M (b, m, n), r (b, m) and c (b, n) must be float32")
+    b, m, n = M.shape
+    if tuple(r.shape) != (b, m) or tuple(c.shape) != (b, n):
+        raise RuntimeError("sinkhorn: r must be (b, m) and c (b, n) for M (b, m, n)")
+    M, r, c = M.contiguous(), r.contiguous(), c.contiguous()
+    L = _lib.lib()
+    nbytes = L.dcd_sinkhorn_workspace_bytes(b, m, n)
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=M.device)
+    P = torch.empty_like(M)
+    iterations = torch.empty((), dtype=torch.int32, device=M.device)
+    st = L.dcd_sinkhorn(_lib.stream_of(M), M.data_ptr(), r.data_ptr(), c.data_ptr(), P.data_ptr(), b, m, n, float(lmbda),
+                        float(max_distance), float(tolerance), int(max_iterations), iterations.data_ptr(), ws.data_ptr(), nbytes)
+    _lib.check(st, "dcd_sinkhorn")
+    return P, iterations
+
+
 def iou_3d(pred_corners, target_corners):
     """(N,8,3) x (N,8,3) -> (N) 3-D IoU (BEV rectangle overlap x height overlap); no gradient."""
     _lib.require_cuda(pred_corners, target_corners)

@@ -789,6 +789,26 @@ int dcd_adamw_apply(void *stream, int ntensors, void *const *params, void *const
 int dcd_gather_rows(void *stream, int n_tables, const void *const *src, void *const *dst, const int64_t *row_bytes,
                     const int64_t *src_rows, const int32_t *index, int B);
 
+/* ------------------------------------------------------------------------------------------------
+ * The Sinkhorn forward of the transport layer without the host (csrc/transport.hip; GMW/lib/optimal_transport.py:52-75).
+ *   K = exp(-lambda min(M, max_distance));  u = r, previous = 1;
+ *   before an iteration: stop when every |u - previous| <= tolerance over the WHOLE batch, or after max_iterations;
+ *   an iteration: previous = u, u = r / (K (c / K^T u));   at the end P = diag(u) K diag(c / K^T u).
+ * ONE call enqueues everything (2 max_iterations + 4 launches) and reads nothing back: the stop is a flag per iteration on the
+ * device, raised with an integer atomic by the kernel that updates u; the launches after the stop return at once.  No kernel
+ * waits for another workgroup.  Every sum runs in a fixed order without floating-point atomics: two calls give the same bits, and
+ * an object's plan depends on its batch mates through the iteration count only.
+ *   M, P        (batch, m, n) fp32, contiguous, distinct (K is built in P's buffer and scaled in place); m, n >= 1, m n < 2^31
+ *   r, c        (batch, m) and (batch, n) fp32, positive
+ *   iterations  one int ON THE DEVICE (or NULL): the number of updates of u that ran
+ *   max_iterations  0 .. 4096;  batch 1 .. 65535
+ *   workspace   dcd_sinkhorn_workspace_bytes(batch, m, n) bytes, 16-byte aligned, dead after the call
+ * 16-byte accesses when n % 4 == 0 and M and P are 16-byte aligned, 4-byte accesses otherwise; the same bits either way.
+ * ---------------------------------------------------------------------------------------------- */
+size_t dcd_sinkhorn_workspace_bytes(int batch, int m, int n);
+int dcd_sinkhorn(void *stream, const float *M, const float *r, const float *c, float *P, int batch, int m, int n, float lambda,
+                 float max_distance, float tolerance, int max_iterations, int *iterations, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
