@@ -47,6 +47,19 @@ class EvalMatchArgs(ctypes.Structure):
     _fields_ = [(n, c_int) for n in _INTS] + [("P", c_int64)] + [(n, c_void_p) for n in _POINTERS]
 
 
+DECODE_MAX_CLASSES = 8
+
+
+class DecodeArgs(ctypes.Structure):
+    """`dcd_decode_args` of include/dcd_hip.h, field for field."""
+    _INTS = ("B", "K", "C", "nk", "n_bins", "num_classes", "ch_box2d", "ch_offset", "ch_corner", "ch_corner_unc", "ch_dims",
+             "ch_ori_cls", "ch_ori_off", "ch_depth", "ch_depth_unc", "ch_kpts2d", "ch_kpts3d", "orientation", "dim_mode",
+             "dim_std_on", "depth_mode", "uncertainty_as_conf", "records")
+    _FLOATS = ("down_ratio", "depth_lo", "depth_hi", "eps")
+    _fields_ = ([(n, c_int) for n in _INTS] + [(n, c_float) for n in _FLOATS] + [("depth_ref", c_float * 2)]
+                + [("dim_mean", c_float * 3 * DECODE_MAX_CLASSES), ("dim_std", c_float * 3 * DECODE_MAX_CLASSES)])
+
+
 # name -> (restype, argtypes); mirrors include/dcd_hip.h one to one
 SIGNATURES = {
     "dcd_version": (ctypes.c_char_p, []),
@@ -159,6 +172,7 @@ SIGNATURES = {
     "dcd_gather_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "dcd_sinkhorn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dcd_sinkhorn": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_size_t]),
+    "dcd_decode_detections": (c_int, [c_void_p] * 7 + [ctypes.POINTER(DecodeArgs)] + [c_void_p] * 4),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

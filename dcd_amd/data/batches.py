@@ -19,7 +19,12 @@ both streams is kept, and only a jump regenerates them from the seed.
 kernels run while the step consumes batch k.  Before a batch is handed over the consuming stream waits for the side stream's
 work on it, and every tensor handed over -- the images and every tensor field of every target -- is `record_stream`'d on the
 consuming stream: the caching allocator would otherwise give their memory back to the side stream's pool, for the batch after
-next to overwrite, while the step still reads it."""
+next to overwrite, while the step still reads it.
+
+Evaluation over a split has a FINITE plan of its own: `EvalPlan(size, batch_size)` gives batch k = images
+[k B, min((k + 1) B, size)) in file order -- the last batch may be short, nothing wraps around, nothing flips -- and
+`EvalBatches(files, pipeline, batch_size, workers=None)` decodes them in a thread pool; `EvalPrefetcher` is the `Prefetcher` that
+stops at the last batch."""
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -137,3 +142,61 @@ class Prefetcher:
             if j not in self._ready:
                 self._produce(j)
         return batch
+
+
+class EvalPlan:
+    """Batch k of an evaluation pass: images [k B, min((k + 1) B, size)) in order, never flipped; `len` = number of batches."""
+
+    def __init__(self, size, batch_size):
+        if batch_size < 1:
+            raise ValueError("batch size %d" % batch_size)
+        if size < 0:
+            raise ValueError("size %d" % size)
+        self.size, self.batch_size = int(size), int(batch_size)
+
+    def __len__(self):
+        return (self.size + self.batch_size - 1) // self.batch_size
+
+    def __call__(self, k):
+        if not 0 <= k < len(self):
+            raise IndexError("batch %d of %d" % (k, len(self)))
+        indices = list(range(k * self.batch_size, min((k + 1) * self.batch_size, self.size)))
+        return indices, [False] * len(indices)
+
+
+class EvalBatches:
+    """`get(k) -> (images, targets)` of `EvalPlan`'s batch k through a `DeviceInputPipeline(is_train=False)`; the frames are read
+    and decoded by `default_workers(workers)` threads."""
+
+    def __init__(self, files, pipeline, batch_size, workers=None):
+        if pipeline.is_train:
+            raise ValueError("evaluation needs a DeviceInputPipeline(is_train=False): it never flips")
+        self.files, self.pipeline, self.batch_size, self.is_train = files, pipeline, int(batch_size), False
+        self.plan = EvalPlan(len(files), batch_size)
+        self._pool = ThreadPoolExecutor(max_workers=default_workers(workers))
+
+    def __len__(self):
+        return len(self.files)
+
+    @property
+    def num_batches(self):
+        return len(self.plan)
+
+    def _read(self, i):
+        return self.files.frame(i), self.files.sample(i)
+
+    def get(self, k):
+        indices, _ = self.plan(k)
+        read = list(self._pool.map(self._read, indices))
+        return self.pipeline([f for f, _ in read], [s for _, s in read], img_ids=[self.files.img_id(i) for i in indices])
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+
+
+class EvalPrefetcher(Prefetcher):
+    """`Prefetcher` over a finite source: nothing is produced past `source.num_batches`."""
+
+    def _produce(self, k):
+        if k < self.source.num_batches:
+            super()._produce(k)

@@ -1,20 +1,111 @@
 """From a KITTI directory to the AP table: the use DGDE/engine/inference.py:19-125 makes of the model, the result writer and
 the evaluator.  One image per model call, as the reference runs its evaluation (TEST.IMS_PER_BATCH = 1); every image's
 `PostProcessor` rows go to `<output_folder>/data/<id>.txt`, then the files are read back and evaluated against `label_2`
-on the device.  No visualisation and no `gen_data` branch."""
+on the device.  No visualisation.
+
+With `batch_size > 1` or `gen_out_dir` the split is walked in batches instead (`_batched_pass`): frames decoded by a thread
+pool, batch k + 1 prepared on a side stream while batch k runs, backbone -> predictor (heads at the top-K cells only) ->
+`PostProcessor.decode_fused` (ONE kernel for the whole decode of the batch), the outputs copied to pinned host memory
+asynchronously, and the host cuts each image's rows at the score threshold and writes its file while the next batch runs.
+The loop never waits on one image: its only waits are one event per batch, a batch late.  With `gen_out_dir` the same pass
+also collects the GMW records (`gen_data_infer.json`).
+
+    python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data] [KEY VALUE ...]
+
+evaluates a saved checkpoint on its own."""
 import logging
 import os
 
+import numpy as np
 import torch
 
 from dcd_amd.eval import kitti_annos, kitti_ap
 
 
-def inference(model, files, pipeline, output_folder, metrics=("R40",)):
+def keep_prefix(raw_scores, threshold):
+    """How many of an image's candidates stay: the raw scores come out of the top-K in descending order, so the rows with
+    score >= threshold are a prefix; returns its length (the first score below the threshold ends it)."""
+    below = ~(np.asarray(raw_scores) >= threshold)                     # (a NaN score is not kept, as `scores >= threshold` drops it)
+    return int(below.argmax()) if below.any() else len(below)
+
+
+def write_image_rows(rows, raw_scores, threshold, path):
+    """One image's decoded candidates (K, 14) -> its result file: the prefix at or above the threshold (an empty file when none).
+    Returns the number of rows kept."""
+    n = keep_prefix(raw_scores, threshold)
+    kitti_annos.write_detections(np.asarray(rows)[:n], path)
+    return n
+
+
+def _records(rows, k2, k3, cat="Car"):
+    """The kept rows of one image in `gen_data.infer_records_batch`'s record layout (numpy views of copies of the pinned slot)."""
+    return [{'kpts_2d': k2[i], 'kpts_3d': k3[i], 'pred_rot': r[12:13], 'box': r[2:6], 'dim': r[6:9], 'pred_location': r[9:12],
+             'score': r[13:14], 'cat': cat} for i, r in enumerate(rows)]
+
+
+def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records):
+    """The batched loop.  Returns {img_id: records} (empty without `want_records`).  Raises NotImplementedError, before anything
+    runs, when the configuration is one `decode_fused` does not cover."""
+    from dcd_amd.data.batches import EvalBatches, EvalPrefetcher
+    pp, predictor = model.heads.post_processor, model.heads.predictor
+    spec = pp.decode_spec()                                            # refuses here, not in the middle of the split
+    device = pipeline.device
+    K, nk = pp.max_detection, spec["nk"]
+    width = 18 + (nk * 5 if want_records else 0)                       # rows (14) | aux (4) | kpts_2d | kpts_3d
+    threshold = pp.det_threshold
+    source = EvalBatches(files, pipeline, batch_size, workers)
+    batches = EvalPrefetcher(source, device)
+    slots = [torch.empty((batch_size * K, width), dtype=torch.float32).pin_memory() for _ in range(2)]
+    views = [s.numpy() for s in slots]
+    events = [torch.cuda.Event() for _ in range(2)]
+    infer_data = {}
+
+    def finish(k, ids):
+        """Host side of batch k, run while batch k + 1 is on the device."""
+        events[k % 2].synchronize()
+        host = views[k % 2]
+        for b, img_id in enumerate(ids):
+            block = host[b * K:(b + 1) * K]
+            n = write_image_rows(block[:, :14], block[:, 14], threshold, os.path.join(predict_folder, img_id + ".txt"))
+            if want_records:
+                kept = block[:n].copy()                                # (the slot is overwritten two batches later)
+                infer_data[img_id] = _records(kept[:, :14], kept[:, 18:18 + nk * 2].reshape(n, nk, 2),
+                                              kept[:, 18 + nk * 2:].reshape(n, nk, 3))
+
+    sparse_before = predictor.sparse_eval_heads
+    predictor.sparse_eval_heads = True
+    try:
+        pending = None
+        for k in range(source.num_batches):
+            images, targets = batches.get(k)
+            feats = model.backbone(images)
+            preds = predictor(feats, targets)
+            rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records)
+            n = rows.shape[0]
+            parts = [rows, aux] + ([recs[0].reshape(n, nk * 2), recs[1].reshape(n, nk * 3)] if want_records else [])
+            slots[k % 2][:n].copy_(torch.cat(parts, dim=1), non_blocking=True)
+            events[k % 2].record()
+            if pending is not None:
+                finish(*pending)
+            pending = (k, [files.img_id(i) for i in source.plan(k)[0]])
+        if pending is not None:
+            finish(*pending)
+    finally:
+        predictor.sparse_eval_heads = sparse_before
+        source.close()
+    return infer_data
+
+
+def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_size=1, workers=None, gen_out_dir=None):
     """model: a `KeypointDetector`; files: a `KittiFiles`; pipeline: a `DeviceInputPipeline(is_train=False)`.
+    batch_size = 1 and gen_out_dir = None: one image per model call, as the reference.  Otherwise the batched pass (see the
+    module docstring); gen_out_dir: where the same pass leaves `gen_data_infer.json`.  A configuration the fused decode does
+    not cover (head-axis orientation, ...) falls back to the one-image loop, and to `generate_infer_data` for the records.
     Returns {metric: the dict of `kitti_ap.official_eval`}."""
     if pipeline.is_train:
         raise ValueError("inference needs a DeviceInputPipeline(is_train=False): evaluation never flips")
+    if batch_size < 1:
+        raise ValueError("batch size %d" % batch_size)
     logger = logging.getLogger("dcd_amd.inference")
     predict_folder = os.path.join(output_folder, "data")
     os.makedirs(predict_folder, exist_ok=True)
@@ -23,10 +114,24 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",)):
     model.eval()
     try:
         with torch.no_grad():
-            for i, img_id in enumerate(ids):
-                images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
-                rows = model(images, targets)[0]
-                kitti_annos.write_detections(rows, os.path.join(predict_folder, img_id + ".txt"))
+            batched = batch_size > 1 or gen_out_dir is not None
+            if batched:
+                try:
+                    infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None)
+                    if gen_out_dir is not None:
+                        from dcd_amd.engine import gen_data
+                        gen_data.dump_gen_data_infer(infer_data, gen_out_dir)
+                except NotImplementedError as e:
+                    logger.info("batched evaluation is not available (%s): one image per call", e)
+                    batched = False
+                    if gen_out_dir is not None:
+                        from dcd_amd.engine.train import generate_infer_data
+                        generate_infer_data(model, files, pipeline, gen_out_dir)
+            if not batched:
+                for i, img_id in enumerate(ids):
+                    images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
+                    rows = model(images, targets)[0]
+                    kitti_annos.write_detections(rows, os.path.join(predict_folder, img_id + ".txt"))
     finally:
         model.train(was_training)
     dt_annos = kitti_annos.read_annos(predict_folder, ids)
@@ -37,3 +142,50 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",)):
                                                        device=pipeline.device)
         logger.info("%s\n%s", metric, text)
     return results
+
+
+def main(argv=None):
+    """`python -m dcd_amd.engine.inference --root KITTI_DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
+    [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
+    import argparse
+    import ast
+    import json
+    from dcd_amd.config import get_cfg
+    from dcd_amd.data.input_pipeline import DeviceInputPipeline
+    from dcd_amd.data.kitti_files import KittiFiles
+    from dcd_amd.engine.train import resume
+    from dcd_amd.model.detector import KeypointDetector
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib")
+    ap.add_argument("--split", default="val")
+    ap.add_argument("--ckpt", required=True)
+    ap.add_argument("--output-dir", required=True)
+    ap.add_argument("--batch", type=int, default=1, help="images per model call (1: the one-image loop)")
+    ap.add_argument("--workers", type=int, default=None)
+    ap.add_argument("--gen-data", action="store_true", help="also write gen_data/gen_data_infer.json from the same pass")
+    ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
+    opts = []
+    for k, v in zip(args.opts[0::2], args.opts[1::2]):
+        try:
+            v = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            pass
+        opts += [k, v]
+    cfg = get_cfg(opts=opts)
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = KeypointDetector(cfg).to(device)
+    resume(args.ckpt, model)
+    files = KittiFiles(args.root, args.split, cfg, is_train=False)
+    pipeline = DeviceInputPipeline(cfg, device, is_train=False)
+    gen_out_dir = os.path.join(args.output_dir, "gen_data") if args.gen_data else None
+    results = inference(model, files, pipeline, os.path.join(args.output_dir, "inference"), metrics=tuple(cfg.TEST.METRIC),
+                        batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir)
+    print(json.dumps({m: {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()} for m, r in results.items()},
+                     default=str))
+    return results
+
+
+if __name__ == "__main__":
+    main()

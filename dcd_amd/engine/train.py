@@ -3,7 +3,7 @@ engine/trainer.py (step, schedule, checkpoint layout), data/batches.py (batch so
 
     arguments = resume(path, model, optimizer, scheduler)            # or {"iteration": 0}
     arguments = do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir,
-                         step=None, log_every=10, val=None)
+                         step=None, log_every=10, val=None, val_batch_size=1)
 
 What it keeps of the reference: the iteration range, `step_schedulers` with the iteration number BEFORE the increment (:152-155),
 the meters of DGDE/utils/metric_logger.py (window 20: median and global average) and the log line (:177-195), the checkpoint
@@ -190,14 +190,17 @@ def generate_infer_data(model, files, pipeline, out_dir):
     return gen_data.dump_gen_data_infer(infer_data, out_dir)
 
 
-def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None):
+def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None,
+             val_batch_size=1):
     """batches: a source of data/batches.py (or a `Prefetcher` around one).  step: `step(images, targets) -> (loss_dict,
     log_loss_dict)`, e.g. a `GraphedTrainStep`; by default `train_step` with SOLVER.GRAD_NORM_CLIP.  val: (files, pipeline) of
     `engine.inference.inference`, run after the final checkpoint; its result comes back as arguments["eval"].
     With TEST.GENERATE_GMW and `val` the validation split is walked TWICE, on purpose: once by `generate_infer_data` for
     `gen_data_infer.json` (backbone, predictor and `forward_batch`, which hands out the key points the records need) and once by
     `inference`, which writes the result files and scores them.  The reference's `do_eval` does both in one loop over its
-    data loader; here the two are separate functions with separate outputs, and the collection pass runs once per trained model."""
+    data loader; here the two are separate functions with separate outputs, and the collection pass runs once per trained model.
+    val_batch_size > 1: the evaluation runs in batches of that many images (`inference(batch_size=...)`), and with
+    TEST.GENERATE_GMW the validation split is walked ONCE: the records and the result files come out of the same pass."""
     logger = logging.getLogger("dcd_amd.trainer")
     is_gen = bool(cfg.TEST.GENERATE_GMW)
     if cfg.SOLVER.LR_WARMUP and warmup_scheduler is None:
@@ -250,7 +253,7 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
         out_dir = os.path.join(output_dir, "gen_data")
         logger.info("Start generate Train data for GMW")
         gen_data.dump_gen_data_train(model.heads.loss_evaluator, out_dir)
-        if val is not None:
+        if val is not None and val_batch_size <= 1:
             logger.info("Start generate Infer data for GMW")
             generate_infer_data(model, val[0], val[1], out_dir)
     else:
@@ -259,7 +262,14 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
                     total / max(1, max_iter - start_iter))
     if val is not None:
         from dcd_amd.engine.inference import inference
-        arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"))
+        if val_batch_size > 1:
+            gen_out_dir = os.path.join(output_dir, "gen_data") if is_gen else None
+            if is_gen:
+                logger.info("Start generate Infer data for GMW (same pass as the evaluation)")
+            arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"), batch_size=val_batch_size,
+                                          gen_out_dir=gen_out_dir)
+        else:
+            arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"))
     return arguments
 
 
@@ -283,6 +293,7 @@ def main(argv=None):
     ap.add_argument("--streaming", action="store_true", help="decode every batch in a thread pool instead of keeping the split in HBM")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--eval-split", default=None, help="evaluate this split after the final checkpoint")
+    ap.add_argument("--eval-batch", type=int, default=1, help="images per model call of that evaluation (1: one image per call)")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
@@ -314,7 +325,8 @@ def main(argv=None):
     if args.eval_split:
         val = (KittiFiles(args.root, args.eval_split, cfg, is_train=False), DeviceInputPipeline(cfg, device, is_train=False))
     batches = source if args.no_prefetch else Prefetcher(source, device)
-    arguments = do_train(cfg, model, optimizer, scheduler, warmup, batches, arguments, args.output_dir, log_every=args.log_every, val=val)
+    arguments = do_train(cfg, model, optimizer, scheduler, warmup, batches, arguments, args.output_dir, log_every=args.log_every, val=val,
+                         val_batch_size=args.eval_batch)
     if hasattr(source, "close"):
         source.close()
     return arguments

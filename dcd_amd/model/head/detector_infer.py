@@ -41,6 +41,10 @@ class PostProcessor(nn.Module):
         self.keypoint_depth_with_uncertainty = 'corner_uncertainty' in heads
         self.use_extra_kpts = 'extra_kpts_2d' in heads
         self.gen_infer_records = []
+        # host copies for `decode_spec` (the encoder keeps these as device tensors: reading them back would synchronise)
+        self._host_stats = (tuple(tuple(float(v) for v in row) for row in head.DIMENSION_MEAN),
+                            tuple(tuple(float(v) for v in row) for row in head.DIMENSION_STD),
+                            tuple(float(v) for v in head.DEPTH_REFERENCE))
 
     _OPTIONAL_FIELDS = ("cls_ids", "target_centers", "dimensions", "rotys", "locations", "offset_3D", "extra_kpts_2d",
                         "extra_kpts_3d", "reg_mask", "Calib_P")
@@ -189,6 +193,73 @@ class PostProcessor(nn.Module):
         info = {'dis_ious': None, 'depth_errors': None, 'uncertainty_conf': confidence, 'estimated_depth_error': depth_error,
                 'vis_scores': raw_scores}
         return (rows, info, vis, rows_image) if batched else (rows, info, vis)
+
+    # ---- the whole decode in one launch (csrc/decode.hip) ---------------------------------------------------------------
+    _FUSED_HEADS = ('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth',
+                    'depth_uncertainty', 'extra_kpts_2d', 'extra_kpts_3d')
+
+    def decode_spec(self):
+        """The configuration `ops.decode_detections` needs, or NotImplementedError with the reason when this configuration is one
+        the kernel does not cover (the caller then keeps `forward` / `forward_batch`)."""
+        from dcd_amd import ops
+        enc, sl = self.anno_encoder, self.key2channel
+        if self.eval_dis_iou or self.eval_depth:
+            raise NotImplementedError("decode_fused: TEST.EVAL_DIS_IOUS / TEST.EVAL_DEPTH are not part of the fused decode")
+        if not enc.multibin:
+            raise NotImplementedError("decode_fused: head-axis orientation is not covered by the kernel (multi-bin only)")
+        missing = [k for k in self._FUSED_HEADS if k not in sl.keys]
+        if missing:
+            raise NotImplementedError("decode_fused needs the heads %s" % ", ".join(missing))
+        nk = self.extra_kpts_num + 10
+        if nk > 128 or self.max_detection > 128:
+            raise NotImplementedError("decode_fused: %d key points / %d detections per image (128 at most each)" % (nk, self.max_detection))
+        if enc.depth_range is None or enc.num_cls > 8 or not 1 <= enc.orien_bin_size <= 4:
+            raise NotImplementedError("decode_fused: no MODEL.HEAD.DEPTH_RANGE, more than 8 classes or more than 4 orientation bins")
+        if enc.dim_modes[0] not in ops.DECODE_DIM_MODE or enc.depth_mode not in ops.DECODE_DEPTH_MODE:
+            raise NotImplementedError("decode_fused: dimension mode %r / depth mode %r" % (enc.dim_modes[0], enc.depth_mode))
+        ch = {"ch_box2d": '2d_dim', "ch_offset": '3d_offset', "ch_corner": 'corner_offset', "ch_corner_unc": 'corner_uncertainty',
+              "ch_dims": '3d_dim', "ch_ori_cls": 'ori_cls', "ch_ori_off": 'ori_offset', "ch_depth": 'depth',
+              "ch_depth_unc": 'depth_uncertainty', "ch_kpts2d": 'extra_kpts_2d', "ch_kpts3d": 'extra_kpts_3d'}
+        spec = {k: sl(v).start for k, v in ch.items()}
+        spec.update(nk=nk, n_bins=enc.orien_bin_size, orientation=ops.DECODE_ORIENTATION["multi-bin"],
+                    dim_mode=ops.DECODE_DIM_MODE[enc.dim_modes[0]], dim_std_on=bool(enc.dim_modes[2]),
+                    depth_mode=ops.DECODE_DEPTH_MODE[enc.depth_mode], uncertainty_as_conf=bool(self.uncertainty_as_conf),
+                    down_ratio=enc.down_ratio, depth_range=tuple(enc.depth_range), depth_ref=self._host_stats[2],
+                    eps=enc.EPS, dim_mean=self._host_stats[0], dim_std=self._host_stats[1])
+        return spec
+
+    def _image_table(self, targets, device):
+        """(B, 16) rows [pad_x, pad_y, width, height, P]: sizes and intrinsics come from the host in ONE copy per distinct set of
+        values (cached by value, as `_rows_P`); the padding is a device field of the targets and is joined on the device."""
+        import numpy as np
+        host = np.stack([np.concatenate((np.asarray(t.size, dtype=np.float32), np.asarray(t.get_field("calib").P, dtype=np.float32).reshape(12)))
+                         for t in targets])
+        key = (host.tobytes(), str(device))
+        if getattr(self, "_table_cache", (None, None))[0] != key:
+            self._table_cache = (key, torch.as_tensor(host).to(device, non_blocking=True))
+        pad = stack_field(targets, "pad_size").to(device=device, dtype=torch.float32)
+        return torch.cat((pad, self._table_cache[1]), dim=1)
+
+    def decode_fused(self, predictions, targets, test=False, records=None):
+        """What `forward_batch` takes -> (rows (B K, 14), aux (B K, 4), records or None) for ALL B K candidates in (image, rank)
+        order, from one kernel launch after the top-K: no score threshold, no `nonzero`, no host synchronisation (the raw scores
+        -- aux[:, 0] -- come out of the top-K descending per image, so the caller keeps a prefix).  aux = raw score, estimated
+        depth error, confidence, arg-max index of the fusion.  records (with TEST.GENERATE_GMW, or records=True) =
+        (K-normalised key points (B K, nk, 2), each row with its own image's intrinsics, 3-D key points (B K, nk, 3)).
+        Raises NotImplementedError for a configuration the kernel does not cover."""
+        from dcd_amd import ops
+        spec = self.decode_spec()
+        if predictions.get('topk') is not None:
+            topk = predictions['topk']
+            vectors = predictions['reg_pois']
+        else:
+            heat, reg = predictions['cls'], predictions['reg']
+            topk = select_topk(heat, K=self.max_detection, fuse_nms=True)
+            vectors = select_point_of_interest(heat.shape[0], topk[1], reg)
+        table = self._image_table(targets, vectors.device)
+        want = self.generate_data if records is None else bool(records)
+        rows, aux, k2, k3 = ops.decode_detections(vectors, topk, table, spec, records=want)
+        return rows, aux, ((k2, k3) if want else None)
 
     def _image_kpts(self, targets, pois, pred_bbox_points, pred_offset_3D):
         k2c = self.key2channel

@@ -1896,3 +1896,60 @@ class _BatchNormActAt(torch.autograd.Function):
 
 def batch_norm_act_at(x, pos, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, relu, group=None):
     return _BatchNormActAt.apply(x, pos, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, relu, group)
+
+
+# ----------------------------------------------------------------------------------------------
+# The eval-time decode of a batch in one launch (csrc/decode.hip, dcd_decode_detections)
+# ----------------------------------------------------------------------------------------------
+DECODE_ORIENTATION = {"multi-bin": 0, "head-axis": 1}
+DECODE_DIM_MODE = {"None": 0, "exp": 1, "linear": 2}
+DECODE_DEPTH_MODE = {"inv_sigmoid": 0, "exp": 1, "linear": 2}
+DECODE_TABLE = 16        # floats per image of the table: pad_x, pad_y, width, height, P (3 x 4)
+
+
+def decode_args(spec, B, K, C, records=False):
+    """The `dcd_decode_args` of a call: `spec` holds the configuration (`PostProcessor.decode_spec`: the channel offsets
+    "ch_*", "nk", "n_bins", "orientation", "dim_mode", "dim_std_on", "depth_mode", "uncertainty_as_conf", "down_ratio",
+    "depth_range", "depth_ref", "eps", and "dim_mean" / "dim_std" as nested lists, one row per class)."""
+    a = _lib.DecodeArgs()
+    a.B, a.K, a.C, a.nk, a.n_bins = int(B), int(K), int(C), int(spec["nk"]), int(spec["n_bins"])
+    mean, std = spec["dim_mean"], spec["dim_std"]
+    a.num_classes = len(mean)
+    for k in ("ch_box2d", "ch_offset", "ch_corner", "ch_corner_unc", "ch_dims", "ch_ori_cls", "ch_ori_off", "ch_depth",
+              "ch_depth_unc", "ch_kpts2d", "ch_kpts3d", "orientation", "dim_mode", "dim_std_on", "depth_mode", "uncertainty_as_conf"):
+        setattr(a, k, int(spec[k]))
+    a.records = int(bool(records))
+    a.down_ratio, a.eps = float(spec["down_ratio"]), float(spec["eps"])
+    a.depth_lo, a.depth_hi = (float(v) for v in spec["depth_range"])
+    a.depth_ref[0], a.depth_ref[1] = (float(v) for v in spec["depth_ref"])
+    if a.num_classes <= _lib.DECODE_MAX_CLASSES:               # (more: the launcher refuses the call)
+        for c in range(a.num_classes):
+            for i in range(3):
+                a.dim_mean[c][i], a.dim_std[c][i] = float(mean[c][i]), float(std[c][i])
+    return a
+
+
+def decode_detections(vectors, topk, image_table, spec, records=False):
+    """Every candidate of a batch decoded in ONE launch: vectors (B, K, C) or (B K, C) head outputs at the top-K cells, topk =
+    (scores, cell index, classes, ys, xs) of `select_topk` ((B, K) each), image_table (B, 16) fp32 rows
+    [pad_x, pad_y, width, height, P].  Returns (rows (B K, 14), aux (B K, 4) = raw score, depth error, confidence, arg-max
+    index, kpts2d (B K, nk, 2) K-normalised or None, kpts3d (B K, nk, 3) or None).  No threshold, no host synchronisation.
+    A configuration the kernel does not cover gives `DcdHipError` (status 1) without a launch."""
+    scores, _, classes, ys, xs = topk
+    _lib.require_cuda(vectors, scores, classes, ys, xs, image_table)
+    L = _lib.lib()
+    B, K = scores.shape
+    vec = _f32c(vectors).reshape(B * K, -1)
+    scores, classes, ys, xs, table = _f32c(scores), _f32c(classes), _f32c(ys), _f32c(xs), _f32c(image_table)
+    if tuple(table.shape) != (B, DECODE_TABLE):
+        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
+    a = decode_args(spec, B, K, vec.shape[1], records)
+    dev = vec.device
+    rows = torch.empty((B * K, 14), dtype=torch.float32, device=dev)
+    aux = torch.empty((B * K, 4), dtype=torch.float32, device=dev)
+    k2 = torch.empty((B * K, a.nk, 2), dtype=torch.float32, device=dev) if records else None
+    k3 = torch.empty((B * K, a.nk, 3), dtype=torch.float32, device=dev) if records else None
+    st = L.dcd_decode_detections(_lib.stream_of(vec), vec.data_ptr(), scores.data_ptr(), classes.data_ptr(), ys.data_ptr(),
+                                 xs.data_ptr(), table.data_ptr(), a, rows.data_ptr(), aux.data_ptr(), _lib.ptr(k2), _lib.ptr(k3))
+    _lib.check(st, "dcd_decode_detections")
+    return rows, aux, k2, k3

@@ -809,6 +809,54 @@ size_t dcd_sinkhorn_workspace_bytes(int batch, int m, int n);
 int dcd_sinkhorn(void *stream, const float *M, const float *r, const float *c, float *P, int batch, int m, int n, float lambda,
                  float max_distance, float tolerance, int max_iterations, int *iterations, void *workspace, size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * The eval-time decode of a whole batch in ONE launch (csrc/decode.hip, arithmetic in csrc/decode_math.h): everything
+ * `PostProcessor._decode` does after the top-K and the POI gather (DGDE/model/head/detector_infer.py:104-213 with the helpers of
+ * DGDE/model/anno_encoder.py): 2-D box, dimensions, direct and key-point depths, the inverse-uncertainty fusion, multi-bin
+ * orientation, the nk dense key points, the edge-constraint depth as the mean over all nk (nk - 1) / 2 pairs (the per-pair
+ * expression of dcd_edge_depth_forward with the clamp [2, 80], minus P[2][3]; the pair tensor is never written), the final
+ * location and the KITTI row.  One workgroup per candidate, B * K candidates; ALL of them are decoded: the score threshold is the
+ * caller's, nothing is counted, nothing is read back.
+ *   vectors      (B K, C) fp32: the regression heads at the top-K cells
+ *   scores, classes, ys, xs   (B K) fp32 each, as dcd_heatmap_topk writes them
+ *   image_table  (B, 16) fp32: pad_x, pad_y, width, height, P (3 x 4 row-major) of each image
+ *   args         the struct below, read during the call only (it travels in the kernel arguments)
+ *   rows         (B K, 14): class, alpha, x1, y1, x2, y2, h, w, l, x, y, z, roty, score
+ *   aux          (B K, 4): raw score, estimated depth error, confidence 1 - clamp(error, 0.01, 1), arg-max index of 1 / sigma
+ *   kpts2d, kpts3d   (B K, nk, 2) K-normalised key points (each row with ITS image's intrinsics) and (B K, nk, 3); written when
+ *                args->records is set, may be NULL otherwise
+ * The pair mean is a fixed-order sum (per-lane partials in pair order, then a tree) without floating-point atomics: two calls
+ * give the same bits.  A candidate's outputs depend on its own inputs only; a non-finite or huge vector gives non-finite
+ * outputs for that candidate and touches nothing else.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer, B < 1, K < 1 or K > 128, nk < 2 or nk > 128, B K > 2^31 - 1,
+ * n_bins outside 1 .. 4, num_classes outside 1 .. 8, a channel range outside [0, C), an orientation other
+ * than DCD_DECODE_ORI_MULTIBIN (head-axis is not supported: the caller keeps its op-by-op decode) or an unknown mode.
+ * ---------------------------------------------------------------------------------------------- */
+#define DCD_DECODE_MAX_CLASSES 8
+#define DCD_DECODE_ORI_MULTIBIN 0
+#define DCD_DECODE_ORI_HEAD_AXIS 1
+#define DCD_DECODE_DIM_NONE 0
+#define DCD_DECODE_DIM_EXP 1
+#define DCD_DECODE_DIM_LINEAR 2
+#define DCD_DECODE_DEPTH_INV_SIGMOID 0
+#define DCD_DECODE_DEPTH_EXP 1
+#define DCD_DECODE_DEPTH_LINEAR 2
+typedef struct {
+    int B, K, C, nk, n_bins, num_classes;
+    /* first channel of each head in a row of `vectors` (key2channel): 2d_dim (4), 3d_offset (2), corner_offset (20),
+     * corner_uncertainty (3), 3d_dim (3), ori_cls (2 n_bins), ori_offset (2 n_bins), depth (1), depth_uncertainty (1),
+     * extra_kpts_2d (2 nk), extra_kpts_3d (3 nk) */
+    int ch_box2d, ch_offset, ch_corner, ch_corner_unc, ch_dims, ch_ori_cls, ch_ori_off, ch_depth, ch_depth_unc, ch_kpts2d, ch_kpts3d;
+    int orientation, dim_mode, dim_std_on, depth_mode;       /* DCD_DECODE_* ; dim_std_on: offset * std + mean instead of offset * mean */
+    int uncertainty_as_conf, records;
+    float down_ratio, depth_lo, depth_hi, eps;
+    float depth_ref[2];
+    float dim_mean[DCD_DECODE_MAX_CLASSES][3], dim_std[DCD_DECODE_MAX_CLASSES][3];
+} dcd_decode_args;
+int dcd_decode_detections(void *stream, const float *vectors, const float *scores, const float *classes, const float *ys,
+                          const float *xs, const float *image_table, const dcd_decode_args *args, float *rows, float *aux,
+                          float *kpts2d, float *kpts3d);
+
 #ifdef __cplusplus
 }
 #endif
