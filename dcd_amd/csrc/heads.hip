@@ -410,10 +410,11 @@ __device__ __forceinline__ float nms_value(const float *__restrict__ hm, int H, 
     return (mx == v) ? v : v * 0.f;  // hm * (hmax == hm).float()
 }
 
-// order-preserving float -> uint key (larger float -> larger key), handles negatives
+// order-preserving float -> uint key (larger float -> larger key), handles negatives; -0.0 + 0.0 = +0.0, so both zeros share one
+// key and tie by index (nms_value writes -0.0 for a negative non-maximum)
 __device__ __forceinline__ unsigned f2key(float f)
 {
-    const unsigned u = __float_as_uint(f);
+    const unsigned u = __float_as_uint(f + 0.f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -646,9 +647,14 @@ __global__ void iou3d_kernel(const float *__restrict__ A, const float *__restric
     const float *a = A + (size_t)n * 24, *b = B + (size_t)n * 24;
     float ax[4], az[4], bx[4], bz[4];
     float min_ha = 0.f, max_ha = 0.f, min_hb = 0.f, max_hb = 0.f;
+    // both footprints in a local frame, origin at the target's corner 0: the edge functions and the shoelace sums below are
+    // differences of products of coordinates, and in camera coordinates (up to 80 m) their fp32 rounding is 2e-4 of the IoU from
+    // 40 m on; the subtraction of two nearby fp32 numbers is exact or nearly so, and the products are then of a few metres
+    // (eval.hip does the same for the same reason)
+    const float ox = b[0], oz = b[2];
     for (int k = 0; k < 4; ++k) {
-        ax[k] = a[k * 3 + 0]; az[k] = a[k * 3 + 2];
-        bx[k] = b[k * 3 + 0]; bz[k] = b[k * 3 + 2];
+        ax[k] = a[k * 3 + 0] - ox; az[k] = a[k * 3 + 2] - oz;
+        bx[k] = b[k * 3 + 0] - ox; bz[k] = b[k * 3 + 2] - oz;
         min_ha -= a[k * 3 + 1]; max_ha -= a[(k + 4) * 3 + 1];
         min_hb -= b[k * 3 + 1]; max_hb -= b[(k + 4) * 3 + 1];
     }
@@ -1002,7 +1008,8 @@ int dcd_focal_loss(void *stream_, const float *pred, const float *target, int64_
 {
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (!pred || !target || !out || n < 0) return DCD_ERR_BAD_ARG;
+    if (!out || n < 0) return DCD_ERR_BAD_ARG;
+    if (n > 0 && (!pred || !target)) return DCD_ERR_BAD_ARG;           // (an empty tensor has no address: n = 0 gives (0, 0))
     if (!dcd_zero_fill(stream, out, 2)) return DCD_ERR_LAUNCH;          // a launch, not a memset node: zero_fill.h
     if (n == 0) return DCD_OK;
     const int grid = grid_for(n, 256 * 4);

@@ -172,7 +172,8 @@ int dcd_edge_depth_backward(void *stream, const float *kps, const float *kps3d, 
  * Penalty-reduced focal loss.  Replaces FocalLoss.forward (DGDE/model/layers/focal_loss.py:57-86).
  * pred, target: n elements.  out[0] = loss sum, out[1] = number of positives (target == 1).
  * grad_pred (n) may be NULL; if given it receives d(loss_sum)/d(pred) (to be scaled by the caller).
- * `out` must be zero-filled by the callee (it is) -- two floats.
+ * `out` must be zero-filled by the callee (it is) -- two floats.  n = 0 gives (0, 0); pred and target may then be NULL.
+ * A target outside [0, 1] contributes no loss, no gradient and no positive; alpha and beta may be any positive numbers.
  * ---------------------------------------------------------------------------------------------- */
 int dcd_focal_loss(void *stream, const float *pred, const float *target, int64_t n, float alpha, float beta,
                    float *out, float *grad_pred);
@@ -208,7 +209,11 @@ size_t dcd_heatmap_topk_workspace_bytes(int B, int C, int H, int W, int K);
  * Point-of-interest gather.  Replaces select_point_of_interest (DGDE/model/layers/utils.py:120-145)
  * without the NCHW->NHWC copy.  feat (B,C,H,W), index (B,M) int64 linear y*W+x -> out (B,M,C).
  * Backward scatters grad_out (B,M,C) into grad_feat (B,C,H,W) with atomics (duplicate indices add);
- * grad_feat must be zero-filled by the caller.
+ * the call ADDS to grad_feat: zero-fill it for a plain gradient, or pass a map to accumulate into.
+ * An index outside [0, H*W) is not an error: the gather returns exactly 0.0 for that row, the scatter writes
+ * nothing for it, whatever M is (both scatter routes, below and from 64 positions per image on).
+ * dcd_patch_scatter_add: a tap whose element index base + (t / 3) * pitch + t % 3 falls outside [0, plane)
+ * is dropped in the same way, tap by tap (the other taps of that window are still added).
  * ---------------------------------------------------------------------------------------------- */
 int dcd_poi_gather(void *stream, const float *feat, const int64_t *index, int B, int C, int H, int W, int M,
                    float *out);
