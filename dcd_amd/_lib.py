@@ -120,6 +120,7 @@ SIGNATURES = {
     "dcd_context_norm_backward": (c_int, [c_void_p] * 5 + [c_int, c_int]),
     "dcd_context_norm_relu_add_forward": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float]),
     "dcd_gmw_refine": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 3),
+    "dcd_gmw_pack_records": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 9),
     "dcd_sum_tensors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64]),
     "dcd_conv3x3_wrw_workspace_bytes": (c_size_t, [c_int] * 5),
     "dcd_conv3x3_wrw": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p, c_size_t]),

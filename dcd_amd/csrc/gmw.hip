@@ -12,6 +12,14 @@
 //   gmw_softmax_depth  one workgroup per object: gathers w and the edge depths at good_idx into LDS (the first 4096; later ones are
 //                      gathered again), softmax with the maximum subtracted (two identical columns give w = 1e15 and a one-hot, not
 //                      a NaN), z = sum softmax * depth, and the location rule: y -= h/2, scale by z / raw_z, y += h/2.
+//   gmw_pack_records   decoded candidates -> GMW's inputs (dcd_gmw_pack_records): one workgroup per record.  The record's 5 nk
+//                      key-point floats go to LDS once; lanes run along the pairs p, so each of the 4 + 6 channel rows of
+//                      e4 (cap, 4, P) / e6 (cap, 6, P) is written contiguously -- 16-byte stores, four pairs per lane, when P % 4 == 0
+//                      and the bases are 16-byte aligned (P = 2628 is), 4-byte stores otherwise.  (i, j) of pair p come from the two
+//                      index tables (`GMW.pair_i` / `pair_j`, read as int32, 16 bytes at a time on the wide path), not from p in closed
+//                      form: the tables ARE the order `edge_expand` uses, and 21 KB of them stay in L2 for every record.  A table entry
+//                      outside [0, nk) gives 0, a source row outside [0, n_rows) a zero record with nothing read.  Pure data movement,
+//                      no atomics: every output is bit-equal to `edge_expand(x[src]).transpose(-2, -1).contiguous()` and the row slices.
 // Every sum runs in a fixed order (a lane's own loop, xor-shuffles, then the waves in index order): no atomics, and an object's
 // result depends neither on its place in the batch nor on B.  An index outside [0, K) makes that object's depth and location NaN.
 #include <hip/hip_runtime.h>
@@ -141,6 +149,87 @@ __global__ __launch_bounds__(256) void gmw_softmax_depth(const float *__restrict
     }
 }
 
+constexpr int GMW_PACK_THREADS = 256;
+constexpr int GMW_PACK_MAX_NK = 128;
+
+__device__ __forceinline__ float gmw_pick(const float *s, int idx, int stride, int c, int nk)
+{
+    return (unsigned)idx < (unsigned)nk ? s[idx * stride + c] : 0.f;
+}
+
+template <int V>
+__global__ __launch_bounds__(GMW_PACK_THREADS) void gmw_pack_records(const float *__restrict__ rows, const float *__restrict__ k2,
+                                                                      const float *__restrict__ k3, int n_rows, int nk,
+                                                                      const int *__restrict__ src, int dst0, int P,
+                                                                      const int *__restrict__ pair_i, const int *__restrict__ pair_j,
+                                                                      float *__restrict__ e4, float *__restrict__ e6,
+                                                                      float *__restrict__ k2_out, float *__restrict__ k3_out,
+                                                                      float *__restrict__ rot, float *__restrict__ loc,
+                                                                      float *__restrict__ dim)
+{
+    __shared__ float s2[GMW_PACK_MAX_NK * 2], s3[GMW_PACK_MAX_NK * 3];
+    const int tid = threadIdx.x;
+    const size_t rec = (size_t)dst0 + blockIdx.x;
+    const int row = src[blockIdx.x];
+    const bool ok = row >= 0 && row < n_rows;                          // uniform over the workgroup
+    const float *a2 = k2 + (size_t)(ok ? row : 0) * nk * 2, *a3 = k3 + (size_t)(ok ? row : 0) * nk * 3;
+    for (int t = tid; t < nk * 2; t += GMW_PACK_THREADS) {
+        const float v = ok ? a2[t] : 0.f;
+        s2[t] = v;
+        k2_out[rec * nk * 2 + t] = v;
+    }
+    for (int t = tid; t < nk * 3; t += GMW_PACK_THREADS) {
+        const float v = ok ? a3[t] : 0.f;
+        s3[t] = v;
+        k3_out[rec * nk * 3 + t] = v;
+    }
+    if (tid < 7) {                                                     // rows: [cls, alpha, box (4), h w l, x y z, ry, score]
+        const float v = ok ? rows[(size_t)row * 14 + 6 + tid] : 0.f;
+        if (tid < 3) dim[rec * 3 + tid] = v;
+        else if (tid < 6) loc[rec * 3 + (tid - 3)] = v;
+        else rot[rec] = v;
+    }
+    __syncthreads();
+    float *o4 = e4 + rec * 4 * (size_t)P, *o6 = e6 + rec * 6 * (size_t)P;
+    for (int p = tid * V; p < P; p += GMW_PACK_THREADS * V) {          // V == 4 only with P % 4 == 0: p + 3 < P
+        int pi[V], pj[V];
+        if constexpr (V == 4) {
+            const int4 ti = *reinterpret_cast<const int4 *>(pair_i + p), tj = *reinterpret_cast<const int4 *>(pair_j + p);
+            pi[0] = ti.x; pi[1] = ti.y; pi[2] = ti.z; pi[3] = ti.w;
+            pj[0] = tj.x; pj[1] = tj.y; pj[2] = tj.z; pj[3] = tj.w;
+        } else {
+            pi[0] = pair_i[p];
+            pj[0] = pair_j[p];
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            float lo[V], hi[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) { lo[v] = gmw_pick(s2, pi[v], 2, c, nk); hi[v] = gmw_pick(s2, pj[v], 2, c, nk); }
+            if constexpr (V == 4) {
+                *reinterpret_cast<float4 *>(o4 + (size_t)c * P + p) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+                *reinterpret_cast<float4 *>(o4 + (size_t)(c + 2) * P + p) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+            } else {
+                o4[(size_t)c * P + p] = lo[0];
+                o4[(size_t)(c + 2) * P + p] = hi[0];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float lo[V], hi[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) { lo[v] = gmw_pick(s3, pi[v], 3, c, nk); hi[v] = gmw_pick(s3, pj[v], 3, c, nk); }
+            if constexpr (V == 4) {
+                *reinterpret_cast<float4 *>(o6 + (size_t)c * P + p) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+                *reinterpret_cast<float4 *>(o6 + (size_t)(c + 3) * P + p) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+            } else {
+                o6[(size_t)c * P + p] = lo[0];
+                o6[(size_t)(c + 3) * P + p] = hi[0];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -164,6 +253,26 @@ int dcd_gmw_refine(void *stream_, const float *f4, const float *f6, const float 
     if (hipGetLastError() != hipSuccess) return DCD_ERR_LAUNCH;
     hipLaunchKernelGGL(gmw_softmax_depth, dim3((unsigned)B), dim3(256), 0, stream, weights, depths, good_idx, num_k, K, raw_location,
                        dim, pred_depth, pred_location);
+    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+}
+
+int dcd_gmw_pack_records(void *stream_, const float *rows, const float *k2, const float *k3, int n_rows, int nk, const int *src, int n,
+                         int dst0, int cap, const int *pair_i, const int *pair_j, float *e4, float *e6, float *k2_out, float *k3_out,
+                         float *rot, float *loc, float *dim)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    if (n < 0 || n_rows < 0 || dst0 < 0 || cap < 0 || (int64_t)dst0 + n > cap || nk < 2 || nk > GMW_PACK_MAX_NK) return DCD_ERR_BAD_ARG;
+    if (!rows || !k2 || !k3 || !src || !pair_i || !pair_j || !e4 || !e6 || !k2_out || !k3_out || !rot || !loc || !dim) return DCD_ERR_BAD_ARG;
+    if (n == 0) return DCD_OK;
+    const int P = nk * (nk - 1) / 2;
+    const bool vec = (P & 3) == 0 && (((uintptr_t)e4 | (uintptr_t)e6 | (uintptr_t)pair_i | (uintptr_t)pair_j) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(gmw_pack_records<4>, dim3((unsigned)n), dim3(GMW_PACK_THREADS), 0, stream, rows, k2, k3, n_rows, nk, src, dst0, P,
+                           pair_i, pair_j, e4, e6, k2_out, k3_out, rot, loc, dim);
+    else
+        hipLaunchKernelGGL(gmw_pack_records<1>, dim3((unsigned)n), dim3(GMW_PACK_THREADS), 0, stream, rows, k2, k3, n_rows, nk, src, dst0, P,
+                           pair_i, pair_j, e4, e6, k2_out, k3_out, rot, loc, dim);
     return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
 }
 

@@ -10,9 +10,15 @@ asynchronously, and the host cuts each image's rows at the score threshold and w
 The loop never waits on one image: its only waits are one event per batch, a batch late.  With `gen_out_dir` the same pass
 also collects the GMW records (`gen_data_infer.json`).
 
-    python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data] [KEY VALUE ...]
+With `gmw=` (a `dcd_amd.gmw.GMW` model) the same pass is the whole two-stage system: the kept candidates of every image batch
+stay on the device, `gmw.RecordRefiner` gathers them into GMW's input layout (`ops.gmw_pack_records`) and refines them in groups
+of `gmw_batch`, and after the last batch the refined files go to `<output_folder>/kitti_results_for_eval` and are scored; the
+result is `results["gmw"]`.  No `gen_data_infer.json` lies between the stages.
 
-evaluates a saved checkpoint on its own."""
+    python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
+                                       [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]
+
+evaluates a saved checkpoint (or, with --gmw-ckpt, a detector and a GMW checkpoint together) on its own."""
 import logging
 import os
 
@@ -43,9 +49,12 @@ def _records(rows, k2, k3, cat="Car"):
              'score': r[13:14], 'cat': cat} for i, r in enumerate(rows)]
 
 
-def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records):
+def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records, refiner=None):
     """The batched loop.  Returns {img_id: records} (empty without `want_records`).  Raises NotImplementedError, before anything
-    runs, when the configuration is one `decode_fused` does not cover."""
+    runs, when the configuration is one `decode_fused` does not cover.  refiner: a `gmw.RecordRefiner`; the decode then always
+    leaves the key points on the device, every batch's kept rows are handed to it (`refiner.add`, a batch late, with the host
+    rows appended to `refiner.host_rows` / `refiner.host_ids` for the writer), and the key points go to the host only with
+    `want_records`."""
     from dcd_amd.data.batches import EvalBatches, EvalPrefetcher
     pp, predictor = model.heads.post_processor, model.heads.predictor
     spec = pp.decode_spec()                                            # refuses here, not in the middle of the split
@@ -60,17 +69,24 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     events = [torch.cuda.Event() for _ in range(2)]
     infer_data = {}
 
-    def finish(k, ids):
+    def finish(k, ids, device_out):
         """Host side of batch k, run while batch k + 1 is on the device."""
         events[k % 2].synchronize()
         host = views[k % 2]
+        kept_src = []
         for b, img_id in enumerate(ids):
             block = host[b * K:(b + 1) * K]
             n = write_image_rows(block[:, :14], block[:, 14], threshold, os.path.join(predict_folder, img_id + ".txt"))
+            if refiner is not None:
+                kept_src.extend(range(b * K, b * K + n))
+                refiner.host_rows.append(block[:n, :14].copy())
+                refiner.host_ids.extend([img_id] * n)
             if want_records:
                 kept = block[:n].copy()                                # (the slot is overwritten two batches later)
                 infer_data[img_id] = _records(kept[:, :14], kept[:, 18:18 + nk * 2].reshape(n, nk, 2),
                                               kept[:, 18 + nk * 2:].reshape(n, nk, 3))
+        if refiner is not None:
+            refiner.add(*device_out, kept_src)                          # (batch k's device tensors are let go after this)
 
     sparse_before = predictor.sparse_eval_heads
     predictor.sparse_eval_heads = True
@@ -80,14 +96,14 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
             images, targets = batches.get(k)
             feats = model.backbone(images)
             preds = predictor(feats, targets)
-            rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records)
+            rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records or refiner is not None)
             n = rows.shape[0]
             parts = [rows, aux] + ([recs[0].reshape(n, nk * 2), recs[1].reshape(n, nk * 3)] if want_records else [])
             slots[k % 2][:n].copy_(torch.cat(parts, dim=1), non_blocking=True)
             events[k % 2].record()
             if pending is not None:
                 finish(*pending)
-            pending = (k, [files.img_id(i) for i in source.plan(k)[0]])
+            pending = (k, [files.img_id(i) for i in source.plan(k)[0]], (rows, recs[0], recs[1]) if refiner is not None else None)
         if pending is not None:
             finish(*pending)
     finally:
@@ -96,11 +112,17 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     return infer_data
 
 
-def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_size=1, workers=None, gen_out_dir=None):
+def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_size=1, workers=None, gen_out_dir=None, gmw=None,
+              gmw_batch=256):
     """model: a `KeypointDetector`; files: a `KittiFiles`; pipeline: a `DeviceInputPipeline(is_train=False)`.
     batch_size = 1 and gen_out_dir = None: one image per model call, as the reference.  Otherwise the batched pass (see the
     module docstring); gen_out_dir: where the same pass leaves `gen_data_infer.json`.  A configuration the fused decode does
     not cover (head-axis orientation, ...) falls back to the one-image loop, and to `generate_infer_data` for the records.
+    gmw: a `dcd_amd.gmw.GMW` model on the pipeline's device: the pass is then always the batched one, the kept candidates are
+    refined on the device in groups of `gmw_batch` (the partition `gmw.refine(data, batch_size=gmw_batch)` makes of the same
+    records), `<output_folder>/kitti_results_for_eval` gets the files of `gmw.write_results` (class "Car", one file per id of
+    the split) and their tables are `results["gmw"] = {metric: dict}`.  With `gmw` a configuration the fused decode does not
+    cover is an error (NotImplementedError): no other route can feed the second stage.
     Returns {metric: the dict of `kitti_ap.official_eval`}."""
     if pipeline.is_train:
         raise ValueError("inference needs a DeviceInputPipeline(is_train=False): evaluation never flips")
@@ -114,14 +136,23 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     model.eval()
     try:
         with torch.no_grad():
-            batched = batch_size > 1 or gen_out_dir is not None
+            batched = batch_size > 1 or gen_out_dir is not None or gmw is not None
+            refiner = None
+            if gmw is not None:
+                from dcd_amd.gmw.inference import RecordRefiner
+                gmw_training = gmw.training
+                gmw.eval()
+                refiner = RecordRefiner(gmw, pipeline.device, batch_size=gmw_batch, nk=model.heads.post_processor.extra_kpts_num + 10)
             if batched:
                 try:
-                    infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None)
+                    infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
+                                               refiner)
                     if gen_out_dir is not None:
                         from dcd_amd.engine import gen_data
                         gen_data.dump_gen_data_infer(infer_data, gen_out_dir)
                 except NotImplementedError as e:
+                    if gmw is not None:
+                        raise NotImplementedError("inference(gmw=...) needs the fused decode, which refuses this configuration: %s" % e)
                     logger.info("batched evaluation is not available (%s): one image per call", e)
                     batched = False
                     if gen_out_dir is not None:
@@ -132,8 +163,12 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
                     images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
                     rows = model(images, targets)[0]
                     kitti_annos.write_detections(rows, os.path.join(predict_folder, img_id + ".txt"))
+            if refiner is not None:
+                pred_location = refiner.finish()
     finally:
         model.train(was_training)
+        if gmw is not None:
+            gmw.train(gmw_training)
     dt_annos = kitti_annos.read_annos(predict_folder, ids)
     gt_annos = kitti_annos.read_annos(os.path.join(files.root, "label_2"), ids)
     results = {}
@@ -141,12 +176,22 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
         text, results[metric] = kitti_ap.official_eval(gt_annos, dt_annos, list(files.classes), metric=metric,
                                                        device=pipeline.device)
         logger.info("%s\n%s", metric, text)
+    if refiner is not None:
+        from dcd_amd.gmw.inference import write_results, writer_fields
+        rows = np.concatenate(refiner.host_rows, 0) if refiner.host_rows else np.zeros((0, 14), np.float32)
+        result_dir = write_results(writer_fields(rows, refiner.host_ids), pred_location,
+                                   os.path.join(output_folder, "kitti_results_for_eval"), ids)
+        refined = kitti_annos.read_annos(result_dir, ids)
+        results["gmw"] = {}
+        for metric in metrics:                                         # class 0, "Car": the one name GMW's files carry
+            text, results["gmw"][metric] = kitti_ap.official_eval(gt_annos, refined, 0, metric=metric, device=pipeline.device)
+            logger.info("GMW %s\n%s", metric, text)
     return results
 
 
 def main(argv=None):
     """`python -m dcd_amd.engine.inference --root KITTI_DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
-    [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
+    [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
     import argparse
     import ast
     import json
@@ -163,6 +208,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=1, help="images per model call (1: the one-image loop)")
     ap.add_argument("--workers", type=int, default=None)
     ap.add_argument("--gen-data", action="store_true", help="also write gen_data/gen_data_infer.json from the same pass")
+    ap.add_argument("--gmw-ckpt", default=None, help="a GMW checkpoint (checkpoint_epoch_N.pth.tar of dcd_amd.gmw.train): refine the "
+                    "kept detections in the same pass and score the refined files as well")
+    ap.add_argument("--gmw-batch", type=int, default=256, help="records per refinement call")
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
@@ -177,13 +225,21 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     model = KeypointDetector(cfg).to(device)
     resume(args.ckpt, model)
+    gmw = None
+    if args.gmw_ckpt:
+        from dcd_amd.gmw import GMW
+        gmw = GMW().to(device)
+        state = torch.load(args.gmw_ckpt, map_location="cpu", weights_only=False)["state_dict"]
+        gmw.load_state_dict({k.replace("module.", ""): v for k, v in state.items()})
     files = KittiFiles(args.root, args.split, cfg, is_train=False)
     pipeline = DeviceInputPipeline(cfg, device, is_train=False)
     gen_out_dir = os.path.join(args.output_dir, "gen_data") if args.gen_data else None
     results = inference(model, files, pipeline, os.path.join(args.output_dir, "inference"), metrics=tuple(cfg.TEST.METRIC),
-                        batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir)
-    print(json.dumps({m: {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()} for m, r in results.items()},
-                     default=str))
+                        batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir, gmw=gmw, gmw_batch=args.gmw_batch)
+
+    def plain(v):
+        return {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else (v.tolist() if hasattr(v, "tolist") else v)
+    print(json.dumps(plain(results), default=str))
     return results
 
 

@@ -191,7 +191,7 @@ def generate_infer_data(model, files, pipeline, out_dir):
 
 
 def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None,
-             val_batch_size=1):
+             val_batch_size=1, val_gmw=None):
     """batches: a source of data/batches.py (or a `Prefetcher` around one).  step: `step(images, targets) -> (loss_dict,
     log_loss_dict)`, e.g. a `GraphedTrainStep`; by default `train_step` with SOLVER.GRAD_NORM_CLIP.  val: (files, pipeline) of
     `engine.inference.inference`, run after the final checkpoint; its result comes back as arguments["eval"].
@@ -200,7 +200,9 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     `inference`, which writes the result files and scores them.  The reference's `do_eval` does both in one loop over its
     data loader; here the two are separate functions with separate outputs, and the collection pass runs once per trained model.
     val_batch_size > 1: the evaluation runs in batches of that many images (`inference(batch_size=...)`), and with
-    TEST.GENERATE_GMW the validation split is walked ONCE: the records and the result files come out of the same pass."""
+    TEST.GENERATE_GMW the validation split is walked ONCE: the records and the result files come out of the same pass.
+    val_gmw: a `gmw.GMW` model; the evaluation is then the batched pass of the whole two-stage system (`inference(gmw=...)`),
+    whatever val_batch_size is, and arguments["eval"]["gmw"] holds the refined detections' tables."""
     logger = logging.getLogger("dcd_amd.trainer")
     is_gen = bool(cfg.TEST.GENERATE_GMW)
     if cfg.SOLVER.LR_WARMUP and warmup_scheduler is None:
@@ -253,7 +255,7 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
         out_dir = os.path.join(output_dir, "gen_data")
         logger.info("Start generate Train data for GMW")
         gen_data.dump_gen_data_train(model.heads.loss_evaluator, out_dir)
-        if val is not None and val_batch_size <= 1:
+        if val is not None and val_batch_size <= 1 and val_gmw is None:
             logger.info("Start generate Infer data for GMW")
             generate_infer_data(model, val[0], val[1], out_dir)
     else:
@@ -262,12 +264,12 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
                     total / max(1, max_iter - start_iter))
     if val is not None:
         from dcd_amd.engine.inference import inference
-        if val_batch_size > 1:
+        if val_batch_size > 1 or val_gmw is not None:
             gen_out_dir = os.path.join(output_dir, "gen_data") if is_gen else None
             if is_gen:
                 logger.info("Start generate Infer data for GMW (same pass as the evaluation)")
             arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"), batch_size=val_batch_size,
-                                          gen_out_dir=gen_out_dir)
+                                          gen_out_dir=gen_out_dir, gmw=val_gmw)
         else:
             arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"))
     return arguments

@@ -5,6 +5,7 @@ train.py train the model from the detector's generated records (main.py:231-341,
 from .model import GMW, pairwise_l2_dist                      # noqa: F401
 from .optimal_transport import RegularisedTransport          # noqa: F401
 from .step import compute_reg_loss, correspondence_loss, gmw_losses, gmw_train_step, gmw_val_step    # noqa: F401
-from .inference import evaluate, extract_features, load_infer_data, refine, write_results    # noqa: F401
+from .inference import (RecordRefiner, evaluate, extract_features, load_infer_data, plan_packs, refine, refine_packed,    # noqa: F401
+                        write_results, writer_fields)
 from .data import ResidentRecords, epoch_order, load_train_data    # noqa: F401
 from .train import train_gmw                                  # noqa: F401

@@ -11,6 +11,11 @@ ray, `GMW_data` (main.py:123-215) rewrites the result files and calls the KITTI 
                     distance matrix nor the transport plan is formed -- refinement reads `1 / diag(M)` only.  `fused=False` is the
                     stock chain (`F.normalize`, the diagonal of `pairwise_l2_dist`, `compute_reg_loss`) in the model's dtype on
                     any device: what the tests measure against, and in float64 their reference;
+  refine_packed     the body of that loop on device tensors that are already in the extractors' layout;
+  RecordRefiner     the same refinement fed from a detector's decode on the device: `ops.gmw_pack_records` gathers the kept
+                    candidates of each image batch into `batch_size` accumulation buffers (`plan_packs` splits a call at the
+                    capacity), a full buffer is refined and its result copied to a pinned slot behind an event;
+  writer_fields     what `write_results` needs beside the locations, from the detector's float32 rows;
   write_results     the files of `GMW_data`, byte for byte;
   evaluate          refine -> write -> `eval.kitti_ap.evaluate`.
 """
@@ -105,6 +110,148 @@ def relocate(raw_location, dim, pred_depth):
     return pred_location
 
 
+def refine_packed(model, e4, e6, k2, k3, rot, loc, dim, compute_z=None):
+    """The refinement of B records that already lie on the device in the layout the extractors take: e4 (B, 4, P) / e6 (B, 6, P)
+    = `edge_expand(k).transpose(-2, -1).contiguous()` (what `ops.gmw_pack_records` writes), k2 (B, 73, 2), k3 (B, 73, 3),
+    rot (B, 1), loc / dim (B, 3), float32.  Returns (pred_depth (B), pred_location (B, 3)) on the device; nothing is read back.
+    `compute_z` defaults to the HIP solver kernel."""
+    from dcd_amd import ops
+    with torch.no_grad():
+        pre_depths, good_idx = (compute_z or ops.compute_z)(k2, k3, rot)
+        f4 = extract_features(model, "FeatureExtractor4d", e4)
+        f6 = extract_features(model, "FeatureExtractor6d", e6)
+        _, z, ploc = ops.gmw_refine(f4, f6, pre_depths, good_idx, loc, dim)
+    return z, ploc
+
+
+def plan_packs(n_new, filled, cap):
+    """How one `RecordRefiner.add` of n_new records goes into buffers of `cap` records that already hold `filled` (< cap): the
+    list of (start, count, flush) pieces -- records [start, start + count) of the call are packed behind what is there, and the
+    buffers are flushed after a piece that fills them.  The pieces cover [0, n_new) in order and none crosses the capacity."""
+    if cap < 1 or not 0 <= filled < cap or n_new < 0:
+        raise ValueError("plan_packs: n_new %d, filled %d, capacity %d" % (n_new, filled, cap))
+    pieces, start = [], 0
+    while start < n_new:
+        count = min(n_new - start, cap - filled)
+        filled += count
+        pieces.append((start, count, filled == cap))
+        start += count
+        filled %= cap
+    return pieces
+
+
+class RecordRefiner:
+    """GMW's refinement fed by a detector's batched decode, without leaving the device: `add` gathers the named candidates of a
+    decoded image batch into `batch_size` accumulation buffers in the extractors' layout (one `ops.gmw_pack_records` launch per
+    piece), and every time the buffers fill they are refined (`refine_packed`) and (z, location) is copied asynchronously into
+    one of two pinned slots with an event.  The records are refined in the groups [0, bs), [bs, 2 bs), ... of the order they
+    were added in -- the partition `refine(data, batch_size=bs)` makes over the same records, so the two give the same bits.
+    The host never waits for a flush it has just issued: a flush first collects the one before it (one `Event.synchronize` per
+    flush, one flush late) and `finish` collects the last.  The row numbers of an `add` go up through two pinned slots, each
+    guarded by the event of the copy that last read it (waited on only if that copy, two calls back, has not finished).
+    Everything is enqueued on the stream current at the call."""
+
+    def __init__(self, model, device, batch_size=256, nk=NUM_KPTS):
+        if nk != NUM_KPTS or int(model.num_kpts) != NUM_KPTS:
+            raise ValueError("RecordRefiner: %d key points (model: %d); GMW's pair tables are for %d"
+                             % (nk, int(model.num_kpts), NUM_KPTS))
+        if batch_size < 1:
+            raise ValueError("batch size %d" % batch_size)
+        if next(model.parameters()).dtype != torch.float32:
+            raise ValueError("RecordRefiner runs in float32 (the model is %s)" % next(model.parameters()).dtype)
+        self.model, self.device, self.cap, self.nk = model, torch.device(device), int(batch_size), nk
+        P = nk * (nk - 1) // 2
+        self.pair_i = model.pair_i.to(device=self.device, dtype=torch.int32).contiguous()
+        self.pair_j = model.pair_j.to(device=self.device, dtype=torch.int32).contiguous()
+        shapes = ((4, P), (6, P), (nk, 2), (nk, 3), (1,), (3,), (3,))        # e4, e6, k2, k3, rot, loc, dim
+        self.buffers = [torch.zeros((self.cap,) + s, dtype=torch.float32, device=self.device) for s in shapes]
+        self.filled = 0
+        self.flushes = 0
+        self._out = [torch.empty((self.cap, 4), dtype=torch.float32).pin_memory() for _ in range(2)]      # z | location
+        self._out_events = [torch.cuda.Event() for _ in range(2)]
+        self._waiting = None                                   # (slot, count) of the flush that has not been collected
+        self._index = [None, None]
+        self._index_events = [None, None]
+        self._adds = 0
+        self._done = []                                        # (count, 4) host arrays, in order
+        self.host_rows, self.host_ids = [], []                 # the caller's notes for the writer: the added records' host rows
+                                                               # (n, 14) per image and each record's image id
+
+    def _upload(self, src_host):
+        slot = self._adds % 2
+        self._adds += 1
+        n = len(src_host)
+        ev = self._index_events[slot]
+        if ev is not None and not ev.query():
+            ev.synchronize()                                   # the copy that last read this slot has finished
+        if self._index[slot] is None or self._index[slot].numel() < n:
+            self._index[slot] = torch.empty(max(n, 1024), dtype=torch.int32).pin_memory()
+        self._index[slot].numpy()[:n] = src_host
+        src = self._index[slot][:n].to(self.device, non_blocking=True)
+        self._index_events[slot] = torch.cuda.Event()
+        self._index_events[slot].record()
+        return src
+
+    def _collect(self):
+        if self._waiting is not None:
+            slot, count = self._waiting
+            self._out_events[slot].synchronize()
+            self._done.append(self._out[slot].numpy()[:count].copy())
+            self._waiting = None
+
+    def _flush(self):
+        count, slot = self.filled, self.flushes % 2
+        z, ploc = refine_packed(self.model, *(b[:count] for b in self.buffers))
+        self._collect()                                        # the flush before this one: its slot is the other one
+        self._out[slot][:count].copy_(torch.cat((z.unsqueeze(1), ploc), dim=1), non_blocking=True)
+        self._out_events[slot].record()
+        self._waiting = (slot, count)
+        self.flushes += 1
+        self.filled = 0
+
+    def add(self, rows, k2, k3, src_host):
+        """rows (n_rows, 14), k2 (n_rows, nk, 2), k3 (n_rows, nk, 3): a decoded batch on the device; src_host: the row numbers to
+        keep, in order (a sequence of ints on the host)."""
+        from dcd_amd import ops
+        src_host = np.asarray(src_host, dtype=np.int32).reshape(-1)
+        if k2.shape[1] != self.nk:
+            raise ValueError("RecordRefiner.add: %d key points per record, %d expected" % (k2.shape[1], self.nk))
+        if len(src_host) == 0:
+            return
+        src = self._upload(src_host)
+        for start, count, flush in plan_packs(len(src_host), self.filled, self.cap):
+            ops.gmw_pack_records(rows, k2, k3, src[start:start + count], self.filled, self.pair_i, self.pair_j, *self.buffers)
+            self.filled += count
+            if flush:
+                self._flush()
+
+    def finish(self):
+        """Flush what is left; returns pred_location (N, 3) float32 on the host (a tensor), in the order the records were added.
+        `pred_depth` (N) is kept as `self.pred_depth`."""
+        if self.filled:
+            self._flush()
+        self._collect()
+        out = np.concatenate(self._done, 0) if self._done else np.zeros((0, 4), np.float32)
+        self._done = []
+        self.pred_depth = torch.from_numpy(out[:, 0].copy())
+        return torch.from_numpy(out[:, 1:].copy())
+
+
+def writer_fields(rows, img_ids):
+    """What `write_results` reads beside the refined locations, from the detector's float32 rows (N, 14) on the host and each
+    row's image id: `img_idx`, and `box`, `score`, `dim_out`, `rot_out` in float64.  A float32 survives `gen_data_infer.json`
+    exactly, so these are the values `load_infer_data` gives for the same records."""
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 14).astype(np.float64)
+    seen, idx = {}, []
+    for img in img_ids:
+        idx.append((img, seen.get(img, 0)))
+        seen[img] = idx[-1][1] + 1
+    if len(idx) != len(rows):
+        raise ValueError("writer_fields: %d rows, %d image ids" % (len(rows), len(idx)))
+    return {"img_idx": idx, "box": rows[:, 2:6].copy(), "score": rows[:, 13].copy(), "dim_out": rows[:, 6:9].copy(),
+            "rot_out": rows[:, 12].copy()}
+
+
 def refine(model, data, device, batch_size=256, fused=True, compute_z=None):
     """`validate`'s refinement over all N records of `data` (load_infer_data) -> (pred_depth (N), pred_location (N, 3)) on the
     host, in the model's dtype.  `compute_z` defaults to the HIP solver kernel; the last, shorter batch goes through as it is."""
@@ -113,23 +260,20 @@ def refine(model, data, device, batch_size=256, fused=True, compute_z=None):
     if compute_z is None:
         from dcd_amd import ops
         compute_z = ops.compute_z
-    if fused:
-        from dcd_amd import ops
-        if dtype != torch.float32:
-            raise ValueError("refine(fused=True) runs in float32 (the model is %s); use fused=False" % dtype)
+    if fused and dtype != torch.float32:
+        raise ValueError("refine(fused=True) runs in float32 (the model is %s); use fused=False" % dtype)
     n = len(data["img_idx"])
     depths, locations = [], []
     with torch.no_grad():
         for s in range(0, n, batch_size):
             k2, k3, rot, loc, dim = (torch.from_numpy(data[k][s:s + batch_size]).to(device=device, dtype=dtype)
                                      for k in ("kpts_2d", "kpts_3d", "pred_rot", "pred_location", "dim"))
-            pre_depths, good_idx = compute_z(k2, k3, rot)
             e4, e6 = model.edge_expand(k2), model.edge_expand(k3)
             if fused:
-                f4 = extract_features(model, "FeatureExtractor4d", e4.transpose(-2, -1).contiguous())
-                f6 = extract_features(model, "FeatureExtractor6d", e6.transpose(-2, -1).contiguous())
-                _, z, ploc = ops.gmw_refine(f4, f6, pre_depths, good_idx, loc, dim)
+                z, ploc = refine_packed(model, e4.transpose(-2, -1).contiguous(), e6.transpose(-2, -1).contiguous(), k2, k3, rot,
+                                        loc, dim, compute_z)
             else:
+                pre_depths, good_idx = compute_z(k2, k3, rot)
                 _, z = compute_reg_loss(pre_depths, _stock_weights(model, e4, e6), loc[:, -1], good_idx)
                 ploc = relocate(loc, dim, z)
             depths.append(z.cpu())

@@ -1638,6 +1638,41 @@ def gmw_refine(f4, f6, depths, good_idx, raw_location, dim):
     return weights, pred_depth, pred_location
 
 
+def gmw_pack_records(rows, k2, k3, src, dst0, pair_i, pair_j, e4, e6, k2_out, k3_out, rot, loc, dim):
+    """Records `src` (int32 row numbers, on the device) of a decoded batch -- rows (n_rows, 14), k2 (n_rows, nk, 2), k3 (n_rows, nk, 3)
+    of `PostProcessor.decode_fused(records=True)` -- written as records dst0 .. dst0 + len(src) - 1 of GMW's input buffers, in
+    place and in one launch: e4 (cap, 4, P) / e6 (cap, 6, P) = `edge_expand(x[src]).transpose(-2, -1).contiguous()` for the pairs
+    of pair_i / pair_j (P int32 each), k2_out / k3_out copies, rot (cap, 1), loc (cap, 3), dim (cap, 3) the rows' columns 12,
+    9-11 and 6-8.  Bit-equal to that chain.  A row number outside [0, n_rows) gives a zero record.  Returns len(src)."""
+    outs = (e4, e6, k2_out, k3_out, rot, loc, dim)
+    _lib.require_cuda(rows, k2, k3, src, pair_i, pair_j, *outs)
+    _require_no_grad("gmw_pack_records", rows, k2, k3, *outs)
+    if k2.dim() != 3 or k3.dim() != 3 or k2.shape[2] != 2 or k3.shape[2] != 3 or k2.shape[:2] != k3.shape[:2]:
+        raise ValueError("gmw_pack_records: k2 %s / k3 %s must be (n_rows, nk, 2) / (n_rows, nk, 3)" % (tuple(k2.shape), tuple(k3.shape)))
+    n_rows, nk = int(k2.shape[0]), int(k2.shape[1])
+    P = nk * (nk - 1) // 2
+    if tuple(rows.shape) != (n_rows, 14):
+        raise ValueError("gmw_pack_records: rows is %s, expected (%d, 14)" % (tuple(rows.shape), n_rows))
+    if src.dim() != 1 or src.dtype != torch.int32 or pair_i.dtype != torch.int32 or pair_j.dtype != torch.int32:
+        raise ValueError("gmw_pack_records: src (n), pair_i and pair_j are int32 tensors")
+    if tuple(pair_i.shape) != (P,) or tuple(pair_j.shape) != (P,):
+        raise ValueError("gmw_pack_records: pair_i %s / pair_j %s must hold nk (nk - 1) / 2 = %d pairs" % (tuple(pair_i.shape), tuple(pair_j.shape), P))
+    cap = int(e4.shape[0]) if e4.dim() == 3 else -1
+    want = ((cap, 4, P), (cap, 6, P), (cap, nk, 2), (cap, nk, 3), (cap, 1), (cap, 3), (cap, 3))
+    if cap < 0 or any(tuple(t.shape) != w for t, w in zip(outs, want)):
+        raise ValueError("gmw_pack_records: the output buffers are %s, expected %s" % ([tuple(t.shape) for t in outs], list(want)))
+    tensors = (rows, k2, k3, src, pair_i, pair_j) + outs
+    if any(t.dtype != torch.float32 for t in (rows, k2, k3) + outs) or not all(t.is_contiguous() for t in tensors):
+        raise ValueError("gmw_pack_records: contiguous float32 tensors expected (the outputs are written in place)")
+    if any(t.device != rows.device for t in tensors):
+        raise ValueError("gmw_pack_records: every tensor must be on %s" % rows.device)
+    n = int(src.shape[0])
+    st = _lib.lib().dcd_gmw_pack_records(_lib.stream_of(rows), rows.data_ptr(), k2.data_ptr(), k3.data_ptr(), n_rows, nk, src.data_ptr(),
+                                         n, int(dst0), cap, pair_i.data_ptr(), pair_j.data_ptr(), *(t.data_ptr() for t in outs))
+    _lib.check(st, "dcd_gmw_pack_records")
+    return n
+
+
 class _FanOut(torch.autograd.Function):
     """n aliases of one tensor whose gradients are summed by ONE kernel (autograd would run n-1 pairwise additions, each
     a read-read-write pass over the map)."""

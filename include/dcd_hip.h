@@ -397,6 +397,23 @@ int dcd_gmw_refine(void *stream, const float *f4, const float *f6, const float *
                    const float *raw_location, const float *dim, int B, int C, int K, float *weights, float *pred_depth,
                    float *pred_location);
 
+/* Decoded candidates -> GMW's inputs, written once (csrc/gmw.hip): what `edge_expand(x).transpose(-2, -1).contiguous()` and the
+ * slices of the detector's rows give, for the records a batched evaluation keeps, straight from `dcd_decode_detections`' outputs.
+ *   rows (n_rows, 14), k2 (n_rows, nk, 2), k3 (n_rows, nk, 3): the decode's outputs.  src: n int32 row numbers (device memory).
+ *   The outputs are buffers of `cap` records; records dst0 .. dst0 + n - 1 are written, the others are left as they are.
+ *   pair_i, pair_j: P = nk (nk - 1) / 2 int32 entries each, pair p = (pair_i[p], pair_j[p]) (`GMW.pair_i` / `pair_j` as int32).
+ *   e4 (cap, 4, P): channels 0-1 = k2[src][i], 2-3 = k2[src][j].  e6 (cap, 6, P): channels 0-2 = k3[src][i], 3-5 = k3[src][j].
+ *   k2_out (cap, nk, 2), k3_out (cap, nk, 3): copies.  rot (cap, 1) = column 12 of the row, loc (cap, 3) = columns 9-11,
+ *   dim (cap, 3) = columns 6-8.
+ * Data movement only: bit-equal to the torch chain; no atomics.  A src entry outside [0, n_rows) writes a zero record and reads
+ * nothing; a table entry outside [0, nk) gives 0.  One workgroup per record; 16-byte stores when P % 4 == 0 and e4, e6 and the
+ * tables are 16-byte aligned.
+ * Status: DCD_OK without a launch for n == 0; DCD_ERR_BAD_ARG, without a launch, for a null pointer, a negative count,
+ * dst0 + n > cap, nk < 2 or nk > 128. */
+int dcd_gmw_pack_records(void *stream, const float *rows, const float *k2, const float *k3, int n_rows, int nk, const int *src, int n,
+                         int dst0, int cap, const int *pair_i, const int *pair_j, float *e4, float *e6, float *k2_out, float *k3_out,
+                         float *rot, float *loc, float *dim);
+
 /* ------------------------------------------------------------------------------------------------
  * Batch normalisation fused with the residual add and ReLU that follow it.  Replaces the stock-op chains
  *   bn -> relu            DGDE/model/backbone/dla_dcn.py:91-93 (BasicBlock), :272-283 (conv levels), :403-410
