@@ -183,7 +183,9 @@ def test_conv3x3_bad_arguments(cuda):
     assert L.dcd_conv3x3(_lib.stream_of(x2), x2.data_ptr(), x2.data_ptr(), x2.data_ptr(), None, x2.data_ptr(), 1, 64, 8, 32, 64, 1, x2.data_ptr(), 1 << 30) == 1      # bias with backward_data
 
 
-@pytest.mark.parametrize("B,C,H,W,f", [(2, 8, 5, 6, 2), (1, 64, 24, 80, 4), (2, 16, 12, 40, 2), (1, 3, 4, 2, 8)])
+@pytest.mark.parametrize("B,C,H,W,f", [(2, 8, 5, 6, 2), (1, 64, 24, 80, 4), (2, 16, 12, 40, 2), (1, 3, 4, 2, 8),
+                                       (1, 2, 7, 300, 2), (1, 2, 7, 300, 4),      # backward row chunks of 3, 3 and a ragged last 1
+                                       (1, 3, 9, 40, 8)])                         # f = 8 on more than one workgroup
 def test_depthwise_upsample_matches_conv_transpose(cuda, B, C, H, W, f):
     """IDAUp's depthwise ConvTranspose2d (csrc/upsample.hip) against torch's conv_transpose2d in fp64."""
     from dcd_amd import ops
@@ -202,7 +204,7 @@ def test_depthwise_upsample_matches_conv_transpose(cuda, B, C, H, W, f):
     _close(wg.grad.cpu(), wd.grad, "grad_weight", 2e-5)
 
 
-@pytest.mark.parametrize("B,C,H,W,f", [(2, 8, 5, 6, 2), (1, 64, 24, 80, 4)])
+@pytest.mark.parametrize("B,C,H,W,f", [(2, 8, 5, 6, 2), (1, 64, 24, 80, 4), (1, 2, 7, 300, 2), (1, 2, 7, 300, 4), (1, 3, 9, 40, 8)])
 def test_depthwise_upsample_with_skip_sum(cuda, B, C, H, W, f):
     """IDAUp's `node(up(x) + skip)`: the sum formed inside the up-sampling kernel (DepthwiseUpsample.forward_add) against
     conv_transpose2d + add in fp64, all three gradients (the skip's is the incoming gradient itself)."""
