@@ -60,6 +60,12 @@ class DecodeArgs(ctypes.Structure):
                 + [("dim_mean", c_float * 3 * DECODE_MAX_CLASSES), ("dim_std", c_float * 3 * DECODE_MAX_CLASSES)])
 
 
+class RecordsArgs(ctypes.Structure):
+    """`dcd_records_args` of include/dcd_hip.h, field for field."""
+    _INTS = ("B", "M", "C", "nk", "n_bins", "ch_offset", "ch_ori_cls", "ch_ori_off", "ch_kpts2d", "ch_kpts3d")
+    _fields_ = [(n, c_int) for n in _INTS] + [("down_ratio", c_float)]
+
+
 # name -> (restype, argtypes); mirrors include/dcd_hip.h one to one
 SIGNATURES = {
     "dcd_version": (ctypes.c_char_p, []),
@@ -174,6 +180,9 @@ SIGNATURES = {
     "dcd_sinkhorn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dcd_sinkhorn": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_size_t]),
     "dcd_decode_detections": (c_int, [c_void_p] * 7 + [ctypes.POINTER(DecodeArgs)] + [c_void_p] * 4),
+    "dcd_gmw_train_records_workspace_bytes": (c_size_t, [c_int] * 3),
+    "dcd_gmw_train_records": (c_int, [c_void_p, c_void_p, ctypes.POINTER(RecordsArgs)] + [c_void_p] * 9 + [c_int] + [c_void_p] * 8
+                              + [c_int, c_int, c_void_p, c_size_t]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

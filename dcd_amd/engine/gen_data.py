@@ -22,6 +22,15 @@ def dump_gen_data_train(loss_evaluator, out_dir="gen_data"):
     return path
 
 
+def dump_gen_data(data, out_dir="gen_data"):
+    """`dump_gen_data_train` for a dict that is already the wire format (`gmw.collect.TrainRecordCollector.gen_data`)."""
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "gen_data_train.json")
+    with open(path, "w") as f:
+        json.dump(data, f, indent=4)
+    return path
+
+
 def infer_records(output, visualize_preds, cat="Car"):
     """One image's detections (N,14) + the PostProcessor's `gen_*` tensors -> list of GMW records."""
     n = output.shape[0]

@@ -190,8 +190,89 @@ def generate_infer_data(model, files, pipeline, out_dir):
     return gen_data.dump_gen_data_infer(infer_data, out_dir)
 
 
+def _pass_plan(batches):
+    """(plan, files) of a batch source of data/batches.py, through a `Prefetcher` as well; None where the source has none.  The
+    plan is a twin of the source's: asking it for a batch moves neither of the source's two streams."""
+    import copy
+    source = getattr(batches, "source", batches)
+    plan = getattr(source, "plan", None)
+    files = getattr(source, "files", None) or getattr(getattr(source, "split", None), "files", None)
+    if plan is not None:
+        plan = copy.copy(plan)
+        plan._next = None
+    return plan, files
+
+
+def _precision(model, tensor):
+    """The bf16 scope `KeypointDetector.forward` and the head open under MODEL.FP16 in training."""
+    import contextlib
+    if not getattr(model, "fp16", False):
+        return contextlib.nullcontext()
+    if tensor.is_cuda:
+        from dcd_amd import _ext
+        return _ext.precision_scope("bf16")
+    return torch.autocast(device_type=tensor.device.type, dtype=torch.bfloat16)
+
+
+def collect_step(model, collector, images, targets, image_numbers):
+    """The body of the collection loop: backbone -> predictor -> `collector.add`.  No loss, no host read."""
+    from dcd_amd.structures.image_list import to_image_list
+    pixels = to_image_list(images).tensors
+    with _precision(model, pixels):
+        features = model.backbone(pixels)
+    with _precision(model.heads, features):
+        predictions = model.heads.predictor(features, targets)
+    reg_pois = predictions.get("reg_pois")
+    if reg_pois is None:
+        raise RuntimeError("the predictor did not evaluate the heads at the objects' centres (`reg_pois`)")
+    collector.add(reg_pois, targets, image_numbers)
+
+
+def collect_gmw_records(model, batches, iterations, start=0, capacity=None, cfg=None):
+    """GMW's training records of batches start .. start + iterations - 1, collected on the device (gmw/collect.py): the model in
+    train mode with its BatchNorm layers frozen and no gradients, as the reference's collection pass runs it
+    (DGDE/engine/trainer.py:97-98, :114-116), but backbone -> predictor -> `dcd_gmw_train_records` only -- the loss is not
+    called.  Returns the `ResidentRecords`; its `collector` attribute is the `TrainRecordCollector` (`gen_data()` for the file).
+    capacity: rows of the tables; by default the number of labelled objects of the images the pass will see, which the host
+    knows from `files.sample`.  Raises NotImplementedError before the first batch for a configuration the kernel refuses."""
+    from dcd_amd.gmw.collect import TrainRecordCollector
+    cfg = cfg if cfg is not None else model.cfg
+    if iterations < 1:
+        raise ValueError("iterations %d" % iterations)
+    device = next(model.parameters()).device
+    B, M = int(batches.batch_size), int(cfg.DATASETS.MAX_OBJECTS)
+    plan, files = _pass_plan(batches)
+    if plan is not None:
+        rows = [plan(k)[0] for k in range(start, start + iterations)]
+    else:
+        rows = [list(range(k * B, (k + 1) * B)) for k in range(start, start + iterations)]
+    if capacity is None:
+        if plan is not None and files is not None:
+            counts = {}
+            for i in {i for r in rows for i in r}:
+                counts[i] = min(len(files.sample(i)["cls"]), M)
+            capacity = max(1, sum(counts[i] for r in rows for i in r))
+        else:
+            capacity = iterations * B * M
+    collector = TrainRecordCollector(cfg, device, capacity, iterations)
+    numbers = torch.tensor(rows, dtype=torch.int32).to(device)          # every iteration's image numbers, one copy before the loop
+    was_training = model.training
+    model.train()
+    freeze_bn(model)
+    try:
+        with torch.no_grad():
+            for it in range(iterations):
+                images, targets = batches.get(start + it)
+                collect_step(model, collector, images, targets, numbers[it])
+    finally:
+        model.train(was_training)
+    records = collector.finish()
+    records.collector = collector
+    return records
+
+
 def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None,
-             val_batch_size=1, val_gmw=None):
+             val_batch_size=1, val_gmw=None, gmw_records=False):
     """batches: a source of data/batches.py (or a `Prefetcher` around one).  step: `step(images, targets) -> (loss_dict,
     log_loss_dict)`, e.g. a `GraphedTrainStep`; by default `train_step` with SOLVER.GRAD_NORM_CLIP.  val: (files, pipeline) of
     `engine.inference.inference`, run after the final checkpoint; its result comes back as arguments["eval"].
@@ -202,7 +283,11 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     val_batch_size > 1: the evaluation runs in batches of that many images (`inference(batch_size=...)`), and with
     TEST.GENERATE_GMW the validation split is walked ONCE: the records and the result files come out of the same pass.
     val_gmw: a `gmw.GMW` model; the evaluation is then the batched pass of the whole two-stage system (`inference(gmw=...)`),
-    whatever val_batch_size is, and arguments["eval"]["gmw"] holds the refined detections' tables."""
+    whatever val_batch_size is, and arguments["eval"]["gmw"] holds the refined detections' tables.
+    gmw_records (with TEST.GENERATE_GMW only): True collects GMW's training records on the device (`collect_gmw_records`) instead
+    of running the loss over the split; arguments["gmw_records"] is then the `ResidentRecords` that `gmw.train.train_gmw` takes,
+    and `gen_data_train.json` is not written.  "json" writes the file as well, from one bulk copy.  A configuration the record
+    kernel refuses raises NotImplementedError before the first batch.  False (the default): the pass and the file as before."""
     logger = logging.getLogger("dcd_amd.trainer")
     is_gen = bool(cfg.TEST.GENERATE_GMW)
     if cfg.SOLVER.LR_WARMUP and warmup_scheduler is None:
@@ -221,10 +306,22 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     elif step is None:
         def step(images, targets):
             return train_step(model, optimizer, images, targets, cfg.SOLVER.GRAD_NORM_CLIP)
+    if gmw_records and not is_gen:
+        raise ValueError("gmw_records needs TEST.GENERATE_GMW: it replaces the collection pass, not the training")
+    if gmw_records not in (False, True, "json"):
+        raise ValueError("gmw_records is False, True or 'json', not %r" % (gmw_records,))
     logger.info("Start training")
     meters, ring = MetricLogger(delimiter=" "), _LogRing(log_every)
     start_time = end = time.time()
-    for iteration in range(start_iter, max_iter):
+    loop = range(start_iter, max_iter)
+    if gmw_records:
+        # the collection on the device: backbone -> predictor -> record kernels, no loss, no read-back per iteration
+        records = collect_gmw_records(model, batches, max_iter - start_iter, start=start_iter, cfg=cfg)
+        freeze_bn(model)
+        arguments["gmw_records"], arguments["iteration"] = records, max_iter
+        logger.info("collected %d records for GMW in %.1f s", len(records), time.time() - start_time)
+        loop = range(0)
+    for iteration in loop:
         images, targets = batches.get(iteration)
         data_time = time.time() - end
         if is_gen:
@@ -253,8 +350,12 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
                 save_checkpoint(output_dir, "model_final", model, optimizer, scheduler, arguments)
     if is_gen:
         out_dir = os.path.join(output_dir, "gen_data")
-        logger.info("Start generate Train data for GMW")
-        gen_data.dump_gen_data_train(model.heads.loss_evaluator, out_dir)
+        if not gmw_records:
+            logger.info("Start generate Train data for GMW")
+            gen_data.dump_gen_data_train(model.heads.loss_evaluator, out_dir)
+        elif gmw_records == "json":
+            logger.info("Start generate Train data for GMW")
+            gen_data.dump_gen_data(arguments["gmw_records"].collector.gen_data(), out_dir)
         if val is not None and val_batch_size <= 1 and val_gmw is None:
             logger.info("Start generate Infer data for GMW")
             generate_infer_data(model, val[0], val[1], out_dir)

@@ -79,7 +79,26 @@ class ResidentRecords:
         self.n = int(data["kpts_2d"].shape[0])
         if self.n < 1:
             raise ValueError("no training records")
-        self.tables = [torch.from_numpy(np.ascontiguousarray(data[k], dtype=np.float32)).to(self.device) for k in KEYS]
+        self._adopt([torch.from_numpy(np.ascontiguousarray(data[k], dtype=np.float32)).to(self.device) for k in KEYS])
+
+    @classmethod
+    def from_device(cls, tables):
+        """Records that already lie in device (or host) memory: {key: float32 tensor (n, ...)} for the four `KEYS`, all on one
+        device, adopted as they are -- views of larger tables included, nothing is copied (gmw/collect.py)."""
+        ts = [tables[k] for k in KEYS]
+        for k, t in zip(KEYS, ts):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ts[0].device:
+                raise ValueError("from_device: %s must be a contiguous float32 tensor on %s" % (k, ts[0].device))
+        self = cls.__new__(cls)
+        self.device = ts[0].device
+        self.n = int(ts[0].shape[0])
+        if self.n < 1:
+            raise ValueError("no training records")
+        self._adopt(ts)
+        return self
+
+    def _adopt(self, tables):
+        self.tables = list(tables)
         for t in self.tables:
             if t.shape[0] != self.n:
                 raise ValueError("the tables of the records disagree in length")

@@ -2,6 +2,10 @@
 
     python -m dcd_amd.gmw.train --train_data_path gen_data/gen_data_train.json --log-dir runs/gmw \\
         [--val_data_path gen_data/gen_data_infer.json --kitti_path /data/kitti]
+    python -m dcd_amd.gmw.train --detector-ckpt runs/dgde/model_final.pth --root /data/kitti/training [--split train] --log-dir runs/gmw
+
+The second form replaces the file: the detector's collection pass writes its records into device tables (gmw/collect.py) and GMW
+trains on them in the same process.
 
 What the reference does per epoch, kept: AdamW(lr, betas (0.9, 0.999), weight decay) at a CONSTANT rate (a `CosineAnnealingLR` is
 built and saved, `scheduler.step()` is never called, main.py:272); from `reg_loss_start_epoch` on the loss weights switch to
@@ -272,7 +276,14 @@ def train_gmw(model, records, log_dir, epochs=100, batch_size=16, lr=1e-4, weigh
 
 def build_parser():
     p = argparse.ArgumentParser(description="Train GMW on the records a trained detector generated")
-    p.add_argument("--train_data_path", required=True, type=str)
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--train_data_path", default=None, type=str, help="gen_data_train.json of a detector's collection pass")
+    src.add_argument("--detector-ckpt", dest="detector_ckpt", default=None, type=str,
+                     help="a detector checkpoint: its records are collected on the device and GMW trains on them, no file in between")
+    p.add_argument("--root", default=None, type=str, help="KITTI directory of the collection pass (with --detector-ckpt)")
+    p.add_argument("--split", default="train", type=str, help="the split the detector's records are collected from")
+    p.add_argument("--detector-batch", dest="detector_batch", default=8, type=int, help="images per detector call of that pass")
+    p.add_argument("--detector-opts", dest="detector_opts", nargs="*", default=[], help="detector configuration overrides: KEY VALUE ...")
     p.add_argument("--val_data_path", default=None, type=str)
     p.add_argument("--kitti_path", default=None, type=str)
     p.add_argument("--log-dir", dest="log_dir", default="", type=str)
@@ -290,6 +301,38 @@ def build_parser():
     return p
 
 
+def records_from_detector(ckpt, root, split="train", batch=8, opts=(), device="cuda:0"):
+    """The collection pass of a trained detector over a KITTI split (`engine.train.collect_gmw_records`): loads the checkpoint, walks
+    the split's labelled images in file order without flips, in whole batches, releases the detector and returns the
+    `ResidentRecords`."""
+    import ast
+    from dcd_amd.config import get_cfg
+    from dcd_amd.data.batches import ResidentBatches
+    from dcd_amd.data.kitti_files import KittiFiles
+    from dcd_amd.data.resident import ResidentSplit
+    from dcd_amd.engine.train import collect_gmw_records, resume
+    from dcd_amd.model.detector import KeypointDetector
+    parsed = []
+    for k, v in zip(list(opts)[0::2], list(opts)[1::2]):
+        try:
+            v = ast.literal_eval(v) if isinstance(v, str) else v
+        except (ValueError, SyntaxError):
+            pass
+        parsed += [k, v]
+    cfg = get_cfg(opts=["MODEL.PRETRAIN", False, "TEST.GENERATE_GMW", True] + parsed)
+    device = torch.device(device)
+    files = KittiFiles(root, split, cfg, is_train=True)
+    model = KeypointDetector(cfg).to(device)
+    resume(ckpt, model)
+    batch = max(1, min(int(batch), len(files)))
+    source = ResidentBatches(ResidentSplit(files, cfg, device), batch, seed=0, is_train=False)
+    iterations = len(files) // batch                            # whole batches, as the reference's pass (trainer.py:97-98)
+    records = collect_gmw_records(model, source, iterations, cfg=cfg)
+    del model, source
+    torch.cuda.empty_cache()
+    return records
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     print(args)
@@ -300,8 +343,14 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("training GMW needs a GPU: the edge-depth solver (dcd_amd.ops.compute_z) has no CPU path")
     from .model import GMW
+    records = args.train_data_path
+    if args.detector_ckpt:
+        if not args.root:
+            raise SystemExit("--detector-ckpt needs --root (the KITTI directory of the collection pass)")
+        records = records_from_detector(args.detector_ckpt, args.root, args.split, args.detector_batch, args.detector_opts)
+        print("collected %d records from %s" % (len(records), args.detector_ckpt))
     model = GMW(device_sinkhorn=True).to(torch.device("cuda:0"))
-    train_gmw(model, args.train_data_path, args.log_dir or ".", epochs=args.epochs, batch_size=args.batch_size, lr=args.lr,
+    train_gmw(model, records, args.log_dir or ".", epochs=args.epochs, batch_size=args.batch_size, lr=args.lr,
               weight_decay=args.weight_decay, cls_weight=args.cls_weight, reg_weight=args.reg_weight,
               reg_loss_start_epoch=args.reg_loss_start_epoch, no_weight_change=args.no_weight_change, print_freq=args.print_freq,
               seed=args.seed or 0, resume=args.resume or None, val_data=args.val_data_path, kitti_root=args.kitti_path)

@@ -15,6 +15,7 @@ from .head import detector_head
 class KeypointDetector(nn.Module):
     def __init__(self, cfg):
         super().__init__()
+        self.cfg = cfg                                                # read by engine.train.collect_gmw_records
         self.fp16 = bool(cfg.MODEL.FP16)
         self.test = cfg.DATASETS.TEST_SPLIT == 'test'
         self.backbone = _backbone.build_backbone_DGDE(cfg)

@@ -879,6 +879,52 @@ int dcd_decode_detections(void *stream, const float *vectors, const float *score
                           const float *xs, const float *image_table, const dcd_decode_args *args, float *rows, float *aux,
                           float *kpts2d, float *kpts3d);
 
+/* ------------------------------------------------------------------------------------------------
+ * GMW's training records of a batch, collected on the device (csrc/records.hip, arithmetic in csrc/records_math.h): what
+ * `Loss_Computation.prepare_predictions` + `generate_data` compute under TEST.GENERATE_GMW (DGDE/model/head/detector_loss.py:148-173,
+ * :217-403), from the regression heads at the objects' centres and the target tables, appended to six tables in device memory.
+ * One call enqueues three launches and reads nothing back:
+ *   1. prepare, one wave per slot (b, m): the key points in image pixels ((kp + centre + GT offset) * 4 - pad), the 3-D key
+ *      points, the TARGET yaw and Calib_P[b, m] in the solver's input layout; an empty slot gets zeros and a unit P;
+ *   2. the edge solver of dcd_edge_depth_forward in its training form over all B M slots: top 1 500 pairs (all pairs where nk
+ *      has fewer), clamp [2, 80], not normalised, minus P[2][3];
+ *   3. finish, one wave per slot: the mean of the slot's kept depths as a fixed-order sum (per-lane partials in rank order, then
+ *      a tree: no floating-point atomics, two calls give the same bits), pred_location and gt_location
+ *      (decode_location_flatten), pred_rot (multi-bin decode_axes_orientation, wrapped to [-pi, pi]), the key points normalised
+ *      with the intrinsics of IMAGE 0 of the batch (the reference's rule), and the row stores.
+ * The finish kernel compacts: the record of slot s goes to row cursor + (number of set reg_mask bytes before s), so records
+ * appear in ascending (b, m) order behind those of the earlier calls.  A row >= cap is not written; the cursor advances all
+ * the same, so the caller sees the overflow when it reads the cursor.  No atomics: every workgroup counts the mask bytes
+ * before its slot itself, and the cursor is a pair -- call number `call` reads cursor[call & 1], and one workgroup writes
+ * cursor[(call + 1) & 1] = that + this call's count and per_call[call] = this call's count.  Before call 0 the caller sets
+ * cursor[0] = 0; calls are numbered 0, 1, 2, ... on one stream.
+ *   reg_pois        (B, M, C) fp32: the regression heads at the target centres
+ *   reg_mask (B, M) u8, target_centers (B, M, 2) i32, offset_3D (B, M, 2), rotys (B, M), locations (B, M, 3),
+ *   calib_P (B, M, 3, 4) fp32, pad_size (B, 2) i64: the target tables;  calib (B, 6) fp32 rows [c_u, c_v, f_u, f_v, b_x, b_y]
+ *   image_numbers   (B) i32: what the `image` table receives for the records of image b
+ *   kpts_2d (cap, nk, 2), kpts_3d (cap, nk, 3), pred_rot (cap, 1), gt_location (cap, 3), pred_location (cap, 3), image (cap) i32
+ *   workspace       dcd_gmw_train_records_workspace_bytes(B, M, nk) bytes (0 for sizes the call refuses), 4-byte aligned,
+ *                   dead after the call: B M x (nk x 5 + 13 + 2 x kept pairs) words -- the solver's inputs, its depths and the
+ *                   pair indices it writes beside them
+ * kpts_3d is a copy of the channels, bit for bit.  Nothing outside the first `cap` rows of the six tables, cursor[(call + 1) & 1],
+ * per_call[call] and the workspace is written, and nothing outside the inputs is read, whatever the inputs hold; a non-finite
+ * `reg_pois` row gives non-finite values in that record only.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer, B < 1, M < 1, nk outside 2 .. 128, n_bins outside 1 .. 4,
+ * cap < 1, call outside [0, n_calls) or a channel range outside [0, C); DCD_ERR_WORKSPACE for a workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, M, C, nk, n_bins;
+    /* first channel of 3d_offset (2), ori_cls (2 n_bins), ori_offset (2 n_bins), extra_kpts_2d (2 nk), extra_kpts_3d (3 nk) */
+    int ch_offset, ch_ori_cls, ch_ori_off, ch_kpts2d, ch_kpts3d;
+    float down_ratio;
+} dcd_records_args;
+size_t dcd_gmw_train_records_workspace_bytes(int B, int M, int nk);
+int dcd_gmw_train_records(void *stream, const float *reg_pois, const dcd_records_args *args, const uint8_t *reg_mask,
+                          const int32_t *target_centers, const float *offset_3D, const float *rotys, const float *locations,
+                          const float *calib_P, const int64_t *pad_size, const float *calib, const int32_t *image_numbers, int cap,
+                          float *kpts_2d, float *kpts_3d, float *pred_rot, float *gt_location, float *pred_location, int32_t *image,
+                          int32_t *cursor, int32_t *per_call, int call, int n_calls, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
