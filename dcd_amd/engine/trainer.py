@@ -24,11 +24,15 @@ _OWN_ADAMW = os.environ.get("DCD_OWN_ADAMW", "1") != "0"      # 0: clip with _fo
 class ClipAdamW(torch.optim.AdamW):
     """`torch.optim.AdamW` (same constructor, same `state` / `state_dict` layout, same `step()`) with one more method:
     `clip_and_step(max_norm)` = `clip_grad_norm_(params, max_norm)` + the non-finite guard + `step()` on csrc/optim.hip -- the gradient
-    norm in one pass, the clip coefficient applied inside the AdamW kernel, 2 048 elements per block: 7 launches and 0.14 ms per step
-    where `_foreach_norm` / `_foreach_mul_` / the library's fused kernel took 29 and 0.43 ms (two blocks per CU at 2 TB/s).  The
-    arithmetic is the library's fused kernel's, operation for operation (tests/test_gpu_optim.py).  Needs what `build_optimizer`
-    sets up on the device: fused + capturable groups with tensor learning rates, fp32 contiguous parameters; anything else falls
-    back to the three library calls."""
+    norm in one pass over blocks of 8 192 elements, the clip coefficient applied inside the AdamW kernel, 4 096 elements per block of
+    the update: 10 launches and 0.18 ms per step where `_foreach_norm` / `_foreach_mul_` / the library's fused kernel took 29 and
+    0.43 ms (two blocks per CU at 2 TB/s).  The update's arithmetic is the library's fused kernel's, operation for operation
+    (tests/test_gpu_optim.py, tests/test_gpu_optim_edges.py).  One difference on purpose: a non-finite norm leaves the GRADIENTS
+    untouched as well as parameters, moments and step counters, where the library calls multiply them by the coefficient
+    max_norm / (norm + 1e-6) of that norm (0 for +inf, NaN for NaN).  Needs what `build_optimizer` sets up on the device: fused +
+    capturable groups with tensor learning rates and Python-number betas / eps / weight_decay, fp32 contiguous parameters; anything
+    else falls back to the three library calls.  The kernels write the parameters through raw pointers, which no version counter
+    sees, so the own-kernel path ends with `ops.invalidate_conv_weights()` (see `ops._PreparedWeights`)."""
 
     def own_kernels_ok(self):
         if not _OWN_ADAMW or getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
@@ -36,6 +40,10 @@ class ClipAdamW(torch.optim.AdamW):
         for g in self.param_groups:
             if not (g.get("fused") and g.get("capturable") and torch.is_tensor(g["lr"]) and g["lr"].is_cuda and g["lr"].dtype == torch.float32
                     and not g["amsgrad"] and not g["maximize"] and not g.get("differentiable")):
+                return False
+            # the hyper-parameters travel by value in the kernel arguments: a tensor there (the library allows it under capturable)
+            # would cost a host sync per step and raise inside a stream capture
+            if any(torch.is_tensor(h) for h in (*g["betas"], g["eps"], g["weight_decay"])):
                 return False
         return True
 
@@ -82,6 +90,9 @@ class ClipAdamW(torch.optim.AdamW):
                                          group["lr"].data_ptr(), float(beta1), float(beta2), float(group["eps"]),
                                          float(group["weight_decay"]), scal.data_ptr()), "dcd_adamw_apply")
         self._opt_called = True                                  # (what the schedulers' call-order check looks at)
+        # the parameters changed behind autograd's version counters: no prepared 3x3 weight of before this step may pass for
+        # current (host-only, so harmless under stream capture, where GraphedTrainStep.replay invalidates after every replay)
+        ops.invalidate_conv_weights(dev)
         return scal[0]
 
 
@@ -396,6 +407,10 @@ def clip_and_step(model, optimizer, grad_norm_clip):
         if isinstance(optimizer, ClipAdamW) and optimizer.own_kernels_ok():
             return optimizer.clip_and_step(grad_norm_clip)
         guard_nonfinite_step(optimizer, clip_grad_norm(_parameters_of(model), grad_norm_clip))
+        optimizer.step()
+        if getattr(optimizer, "found_inf", None) is not None:
+            optimizer.found_inf = None                           # the guard's flag belongs to this step (own_kernels_ok looks at it)
+        return
     optimizer.step()
 
 

@@ -1053,10 +1053,15 @@ class _PreparedWeights:
 
     A layer enters the table the first time `_Conv3x3.forward` sees its weight (that call still transforms its own copy).
     An entry is only used while it is provably current: same storage, and `weight._version` equal to the version the last
-    refresh transformed -- an optimizer step, a `load_state_dict` or any other in-place write in between sends the call back
-    to its own transform (a write that BYPASSES the version counter -- `p.data.*`, a raw-pointer kernel, a replayed graph that
-    is not GraphedTrainStep -- must be followed by `invalidate_conv_weights()`).  Entries hold weak references; a dead weight
-    drops out at the next refresh.
+    refresh transformed -- a `load_state_dict` or any other in-place write through autograd's counters in between sends the call
+    back to its own transform (a write that BYPASSES the version counter -- `p.data.*`, a raw-pointer kernel, a replayed graph
+    that is not GraphedTrainStep -- must be followed by `invalidate_conv_weights()`).  Optimizer steps are such writes: the
+    library's FUSED Adam / AdamW kernels update the parameters without touching their version counters (the foreach and
+    single-tensor forms do bump them), and csrc/optim.hip writes through `data_ptr()`.  So the table invalidates itself after
+    every `Optimizer.step()` of the process (a global step post-hook, installed with the first registered layer), the own-kernel
+    path of `ClipAdamW.clip_and_step` ends with `invalidate_conv_weights()`, and `GraphedTrainStep.replay` invalidates after every
+    replay.  Without these a grad-enabled forward that followed a step without a refresh in between ran on the weights of before
+    that step (tests/test_gpu_prepared_weights.py).  Entries hold weak references; a dead weight drops out at the next refresh.
 
     HIP graphs: a captured `refresh()` bakes the address of `self.table` into the graph, a captured convolution the
     addresses of its entry's buffers.  From the first lookup / refresh under capture on, nothing a capture may have seen is ever
@@ -1104,6 +1109,7 @@ class _PreparedWeights:
             tb = torch.empty(L.dcd_conv3x3_weights_bytes(Ci, Co, 1) // 4, dtype=torch.float32, device=weight.device)
         self.entries[id(weight)] = [weakref.ref(weight), weight.data_ptr(), tf, tb, -1, 0]
         self.dirty = True
+        _watch_optimizer_steps()
 
     def refresh(self):
         if not self.entries or not _PREP_TABLE:
@@ -1144,6 +1150,25 @@ class _PreparedWeights:
 
 _PREPARED = {}                     # (device index, layout: False fp32 | True split | "bf16" direct) -> _PreparedWeights
 _LAYOUT_KEYS = (False, True, "bf16")
+
+
+_STEP_HOOK = None
+
+
+def _invalidate_all_conv_weights(*_):
+    for p in _PREPARED.values():
+        for e in p.entries.values():
+            e[4] = -1
+
+
+def _watch_optimizer_steps():
+    """Every `torch.optim.Optimizer.step()` from now on marks all table entries stale (host-only: a loop over the entries; inside
+    a stream capture it runs at capture time, the replays are GraphedTrainStep's business).  The version counters cannot be
+    relied on for this: the library's fused optimizer kernels leave them as they were."""
+    global _STEP_HOOK
+    if _STEP_HOOK is None:
+        from torch.optim.optimizer import register_optimizer_step_post_hook
+        _STEP_HOOK = register_optimizer_step_post_hook(_invalidate_all_conv_weights)
 
 
 def invalidate_conv_weights(device=None):

@@ -10,10 +10,10 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(64, 64, 3, 3), (256,), (27, 64, 3, 3), (1,), (3, 5, 7), (2048,), (2049,), (512, 256, 3, 3), (4097, 3), (16, 3, 7, 7)]
 
 
-def _pair(cuda, seed, n_extra=0, lr=3e-4, blr=6e-4, wd=1e-5):
+def _pair(cuda, seed, n_extra=0, lr=3e-4, blr=6e-4, wd=1e-5, shapes=None):
     from dcd_amd.engine import trainer
     g = torch.Generator().manual_seed(seed)
-    shapes = SHAPES + [(33,)] * n_extra
+    shapes = (SHAPES if shapes is None else shapes) + [(33,)] * n_extra
     make = lambda: [torch.nn.Parameter(torch.randn(*s, generator=torch.Generator().manual_seed(seed + i)).to(cuda)) for i, s in enumerate(shapes)]
     pa, pb = make(), make()
     def opt(cls, ps):
@@ -109,9 +109,11 @@ def test_non_finite_norm_freezes_everything(cuda):
 
 
 def test_many_tensors_span_several_launches(cuda):
-    """More tensors than one launch's argument table holds (64), an element count of one among them."""
+    """More tensors than any launch's argument table holds (csrc/optim.hip: 80 tensors per launch of the update, 240 gradients per
+    launch of the norm, 448 step counters per launch), an element count of one among them."""
     from dcd_amd.engine import trainer
-    pa, pb, oa, ob, g = _pair(cuda, 4, n_extra=150)
+    pa, pb, oa, ob, g = _pair(cuda, 4, n_extra=460)
+    assert sum(1 for p in pa if p.dim() <= 1) > 448 and len(pa) > 240       # the bias group alone overflows every table
     for it in range(2):
         _set_grads(pa, pb, g, 5.0)
         ta = oa.clip_and_step(15.0)
@@ -119,6 +121,104 @@ def test_many_tensors_span_several_launches(cuda):
         trainer.guard_nonfinite_step(ob, tb)
         ob.step()
         assert abs(float(ta) - float(tb)) <= 2e-6 * float(tb)
+    for a, b in zip(pa, pb):
+        assert torch.allclose(a, b, rtol=2e-6, atol=1e-8)
+
+
+DP_SHAPES = [(27,), (16, 3, 7, 7), (1,), (4097, 3), (64, 64, 3, 3), (5,)]
+
+
+def test_clip_and_step_on_the_data_parallel_gradient_layout(cuda):
+    """`GraphedTrainStep(distributed=True)` makes every `.grad` a view of ONE flat buffer, packed back to back: after the first
+    parameter with an odd element count most gradients sit at 4-byte alignment and the kernels take their scalar loops.  Three
+    steps with the clip active against the library on separate tensors, at the bounds of
+    test_clip_and_step_equals_the_library_calls; the flat buffer afterwards is the concatenation of the library's clipped
+    gradients (nothing written across a view's end), the words behind it untouched."""
+    from dcd_amd.engine import trainer
+    pa, pb, oa, ob, g = _pair(cuda, 6, shapes=DP_SHAPES)
+    assert oa.own_kernels_ok()
+    total_elems = sum(p.numel() for p in pa)
+    store = torch.full((total_elems + 4,), -7.25, device=cuda)
+    flat = store[:total_elems]
+    views, o = [], 0
+    for p in pa:                                                 # trainer.GraphedTrainStep.__init__, the `_flat` set-up
+        views.append(flat[o:o + p.numel()].view_as(p))
+        o += p.numel()
+    assert flat.data_ptr() % 16 == 0 and sum(1 for v in views if v.data_ptr() % 16 != 0) >= 3
+    gmax = [0.0] * len(pa)
+    for it in range(3):
+        for a, b, v in zip(pa, pb, views):
+            gr = (torch.randn(a.shape, generator=g) * 30.0).to(cuda)
+            v.copy_(gr)
+            a.grad, b.grad = v, gr.clone()
+        total = oa.clip_and_step(15.0)
+        ref_total = trainer.clip_grad_norm(pb, 15.0)
+        trainer.guard_nonfinite_step(ob, ref_total)
+        ob.step()
+        assert float(ref_total) > 15.0                           # the clip is active: every view is rewritten
+        assert abs(float(total) - float(ref_total)) <= 2e-6 * float(ref_total)
+        assert all(a.grad.data_ptr() == v.data_ptr() for a, v in zip(pa, views))
+        assert torch.allclose(flat, torch.cat([b.grad.reshape(-1) for b in pb]), rtol=2e-6, atol=0), "flat gradient buffer at step %d" % it
+        assert torch.equal(store[total_elems:], torch.full((4,), -7.25, device=cuda))
+        gmax = [max(m, a.grad.abs().max().item()) for m, a in zip(gmax, pa)]
+    for i, (a, b) in enumerate(zip(pa, pb)):
+        sa, sb = oa.state[a], ob.state[b]
+        assert float(sa["step"]) == float(sb["step"]) == 3.0
+        assert torch.allclose(a, b, rtol=2e-6, atol=1e-8), "parameter %d: %.3e" % (i, (a - b).abs().max().item())
+        assert (sa["exp_avg"] - sb["exp_avg"]).abs().max().item() <= 2e-7 * gmax[i], i
+        assert (sa["exp_avg_sq"] - sb["exp_avg_sq"]).abs().max().item() <= 2e-7 * gmax[i] ** 2, i
+
+
+def test_tensor_hyper_parameters_take_the_library_path(cuda):
+    """betas / eps / weight_decay as tensors (the library allows them under capturable): `own_kernels_ok()` is False, since the
+    kernels take them by value -- a device tensor there would cost a host sync per step and raise inside a capture -- and
+    `trainer.clip_and_step` then runs the library calls, whose result it still equals."""
+    from dcd_amd.engine import trainer
+    for key, value in (("weight_decay", torch.tensor(1e-5, device=cuda)), ("eps", torch.tensor(1e-8, device=cuda)),
+                       ("betas", (torch.tensor(0.9, device=cuda), 0.99))):
+        pa, pb, oa, ob, g = _pair(cuda, 8)
+        assert oa.own_kernels_ok()
+        for grp in oa.param_groups:
+            grp[key] = value
+        assert not oa.own_kernels_ok(), key
+    pa, pb, oa, ob, g = _pair(cuda, 8)
+    for grp in oa.param_groups + ob.param_groups:
+        grp["weight_decay"] = torch.tensor(1e-5, device=cuda)
+    model = torch.nn.ParameterList(pa)
+    for it in range(2):
+        _set_grads(pa, pb, g, 30.0)
+        trainer.clip_and_step(model, oa, 15.0)
+        _library_step(trainer, ob, pb, 15.0)
+    for a, b in zip(pa, pb):
+        assert float(oa.state[a]["step"]) == 2.0
+        assert torch.allclose(a.grad, b.grad, rtol=2e-6, atol=0)
+        assert torch.allclose(a, b, rtol=2e-6, atol=1e-8)
+
+
+def test_a_fallback_step_does_not_disable_the_own_kernels(cuda, monkeypatch):
+    """The module-level `trainer.clip_and_step` fallback sets `optimizer.found_inf` for the library's fused kernel; it must clear it
+    after the step, as the class's own fallback does: `own_kernels_ok()` looks at it, so a flag left behind kept every later step
+    on the library path."""
+    from dcd_amd.engine import trainer
+    pa, pb, oa, ob, g = _pair(cuda, 9)
+    model = torch.nn.ParameterList(pa)
+    calls = []
+    real = trainer.ClipAdamW.clip_and_step
+    monkeypatch.setattr(trainer.ClipAdamW, "clip_and_step", lambda self, mn: (calls.append(1), real(self, mn))[1])
+    for grp in oa.param_groups:
+        grp["weight_decay"] = torch.tensor(1e-5, device=cuda)    # not eligible: the library path
+    _set_grads(pa, pb, g, 1.0)
+    assert not oa.own_kernels_ok()
+    trainer.clip_and_step(model, oa, 15.0)
+    _library_step(trainer, ob, pb, 15.0)
+    assert not calls and getattr(oa, "found_inf", None) is None
+    for grp in oa.param_groups:
+        grp["weight_decay"] = 1e-5                               # eligible again
+    assert oa.own_kernels_ok()
+    _set_grads(pa, pb, g, 1.0)
+    trainer.clip_and_step(model, oa, 15.0)
+    _library_step(trainer, ob, pb, 15.0)
+    assert calls and float(oa.state[pa[0]]["step"]) == 2.0
     for a, b in zip(pa, pb):
         assert torch.allclose(a, b, rtol=2e-6, atol=1e-8)
 
