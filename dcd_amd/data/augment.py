@@ -7,7 +7,10 @@ place; here a new dict comes back and the input is left alone.
 Types follow the reference: the box is flipped in float64 from the values given (`obj.xmin` / `obj.xmax` are the parsed
 floats, not the float32 `box2d`); it stays float64 in the result, as `obj.xmin` does, and is rounded to float32 where the
 encoder packs it (`pack_raw`), which is where `obj.box2d` is rounded.  Rounding the box first and flipping it then can land
-one float32 step away.  `t` is the float32 array `Object3d` keeps, `ry` / `alpha` are Python floats.  `kpts3d` is NOT mirrored: the reference leaves the object-frame key points alone (its own comment at
+one float32 step away.  The one exception is a sample marked `box2d_float32=True` (a right-camera view of
+`KittiFiles`): the reference overwrites `obj.xmin .. obj.ymax` of such a view with float32 scalars, so its flip runs in float32
+under NumPy >= 2, the NumPy that wrote tests/golden/right_views.npz; that box is flipped in float32 here and stays float32.
+`t` is the float32 array `Object3d` keeps, `ry` / `alpha` are Python floats.  `kpts3d` is NOT mirrored: the reference leaves the object-frame key points alone (its own comment at
 augmentations.py:71), and tests/golden/target_encoding_flipped.npz pins that."""
 import math
 
@@ -28,10 +31,18 @@ def flip_sample(sample):
     """Raw label values of one image -> the values after a horizontal flip (a new dict; arrays are copies)."""
     img_w = int(sample["image_size"][0])
     out = dict(sample)
-    box = np.array(sample["box2d"], dtype=np.float64).reshape(-1, 4)
-    w = box[:, 2] - box[:, 0]                                       # augmentations.py:47-50
-    box[:, 0] = img_w - box[:, 2] - 1
-    box[:, 2] = box[:, 0] + w
+    if sample.get("box2d_float32", False):
+        # a right view (kitti.py:290-293): `obj.xmin .. obj.ymax` are float32 scalars there, and NumPy >= 2 keeps
+        # `int - float32 - int` in float32 (the Python integers are weak), one rounding per operation
+        box = np.array(sample["box2d"], dtype=np.float32).reshape(-1, 4)
+        w = box[:, 2] - box[:, 0]
+        box[:, 0] = np.float32(img_w) - box[:, 2] - np.float32(1)
+        box[:, 2] = box[:, 0] + w
+    else:
+        box = np.array(sample["box2d"], dtype=np.float64).reshape(-1, 4)
+        w = box[:, 2] - box[:, 0]                                   # augmentations.py:47-50
+        box[:, 0] = img_w - box[:, 2] - 1
+        box[:, 2] = box[:, 0] + w
     out["box2d"] = box                                              # float32 where the encoder packs it, like `obj.box2d` (:50)
     t = np.array(sample["t"], dtype=np.float32).reshape(-1, 3)      # :68-70
     t[:, 0] = -t[:, 0]

@@ -7,6 +7,9 @@ Two sources share one interface -- `source.batch_size`, `len(source)` (images) a
                                                  PNG decode in a thread pool -> `DeviceInputPipeline` with explicit `flip=`;
                                                  for a split that does not fit in device memory, and the plain path
 
+`len(source)` counts the indices of the `files` object behind it: with `DATASETS.USE_RIGHT_IMAGE` those are 2 n views of n images
+(`KittiFiles`), the sampler draws from all of them, and a resident split's tables have 4 n rows (two views times two flips).
+
 Batch k is a PURE FUNCTION of (seed, rank, world_size, k) for both: its images are positions [k B, (k + 1) B) of the rank's
 `TrainingSampler` stream, its flip flags are draws [k B, (k + 1) B) of one `random.Random` stream seeded from (seed, rank), each
 `random() < INPUT.AUG_PARAMS[0][0]` as `DeviceInputPipeline.draw_flips` draws them; an evaluation source walks the images in

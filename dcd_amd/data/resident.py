@@ -12,11 +12,16 @@ is not safe), go up in chunks through one reused pinned staging buffer, and stay
 
 What is resident:
   frames    one uint8 tensor, every frame packed HWC at a multiple of 64 bytes (the layout of `DeviceInputPipeline._pack`)
-  six tables of 2 N rows, row 2 i + flip for image i, built on the host with `pack_raw` from `files.sample(i)` and from
-  `flip_sample(files.sample(i))` -- the flip arithmetic stays the host's float64, nothing changes numerically:
+  six tables of 2 N rows, row 2 i + flip for index i of `files`, built on the host with `pack_raw` from `files.sample(i)` and
+  from `flip_sample(files.sample(i))` -- the flip arithmetic stays the host's (float64; float32 for the box of a right-camera
+  view, as the reference flips it), nothing changes numerically:
     records (5) int64 (byte offset, pitch, h, w, flip) | objs (M,16) f64 | kpts3d (M,n_extra,3) f64 | P (3,4) f64 |
     size (2) i32 | count () i32
-  Both P matrices of every image stay on the host as well, for the `Calibration` objects of the targets.
+  Both P matrices of every index stay on the host as well, for the `Calibration` objects of the targets.
+N is `len(files)`, the number of VIEWS: with `DATASETS.USE_RIGHT_IMAGE` a `KittiFiles` of n images has N = 2 n indices (index
+i >= n: the right-camera view of image i - n), so the frame buffer holds both cameras' frames -- `trainval` is then 14 962 frames,
+about 20.8 GB -- and the tables have 4 n rows, two views times two flips per image.  Frame size, byte offset and `P` are looked up
+per index, never per image id (two indices share one), and `nbytes`, which `max_bytes` refuses, is computed from the views.
 
 `batch` checks the indices on the host, copies B int32 row numbers from a two-slot pinned buffer (events guard the slots, as in
 the pipeline), gathers the six tables' rows in one launch (`dcd_gather_rows`), and runs the pipeline's own two kernels on the

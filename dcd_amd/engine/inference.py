@@ -18,7 +18,10 @@ result is `results["gmw"]`.  No `gen_data_infer.json` lies between the stages.
     python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
                                        [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]
 
-evaluates a saved checkpoint (or, with --gmw-ckpt, a detector and a GMW checkpoint together) on its own."""
+evaluates a saved checkpoint (or, with --gmw-ckpt, a detector and a GMW checkpoint together) on its own.  `--split test` reads
+`ImageSets/test.txt`, the images and `calib` only and writes one result file per id, in `inference/data` and, with --gmw-ckpt,
+in `inference/kitti_results_for_eval`: the files of a leaderboard entry.  Nothing is scored then and the printed result is `{}`
+or `{"gmw": {}}`.  `DATASETS.INFER_ON_RIGHT_IMG True` runs either kind of split on `image_3` with `P3`."""
 import logging
 import os
 
@@ -123,7 +126,9 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     records), `<output_folder>/kitti_results_for_eval` gets the files of `gmw.write_results` (class "Car", one file per id of
     the split) and their tables are `results["gmw"] = {metric: dict}`.  With `gmw` a configuration the fused decode does not
     cover is an error (NotImplementedError): no other route can feed the second stage.
-    Returns {metric: the dict of `kitti_ap.official_eval`}."""
+    Returns {metric: the dict of `kitti_ap.official_eval`}.
+    A `files` whose `has_labels` is false (KITTI's `test` split; an object without the attribute counts as labelled) goes through
+    the same pass and only leaves its files behind: see `finish_pass`."""
     if pipeline.is_train:
         raise ValueError("inference needs a DeviceInputPipeline(is_train=False): evaluation never flips")
     if batch_size < 1:
@@ -169,23 +174,46 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
         model.train(was_training)
         if gmw is not None:
             gmw.train(gmw_training)
-    dt_annos = kitti_annos.read_annos(predict_folder, ids)
-    gt_annos = kitti_annos.read_annos(os.path.join(files.root, "label_2"), ids)
-    results = {}
-    for metric in metrics:
-        text, results[metric] = kitti_ap.official_eval(gt_annos, dt_annos, list(files.classes), metric=metric,
-                                                       device=pipeline.device)
-        logger.info("%s\n%s", metric, text)
+    refined = None
     if refiner is not None:
-        from dcd_amd.gmw.inference import write_results, writer_fields
         rows = np.concatenate(refiner.host_rows, 0) if refiner.host_rows else np.zeros((0, 14), np.float32)
-        result_dir = write_results(writer_fields(rows, refiner.host_ids), pred_location,
-                                   os.path.join(output_folder, "kitti_results_for_eval"), ids)
-        refined = kitti_annos.read_annos(result_dir, ids)
+        refined = (rows, refiner.host_ids, pred_location)
+    return finish_pass(files, ids, output_folder, metrics, pipeline.device, refined)
+
+
+def finish_pass(files, ids, output_folder, metrics, device, refined=None):
+    """The host half that follows the pass over the split: `<output_folder>/data` holds the detector's files by now.
+    refined: (rows (n, 14) float32 on the host, each row's image id, the refined locations (n, 3)) of a pass with `gmw`; the files
+    of `gmw.write_results` then go to `<output_folder>/kitti_results_for_eval`, one per id of the split.
+    A labelled split is scored against `label_2`: {metric: dict}, and `results["gmw"] = {metric: dict}` for the refined files.
+    A split without labels (`files.has_labels` false: KITTI's `test`) is only written: every id must have its file in `data`
+    (an empty one where nothing passed the threshold), no label file is opened, nothing is scored, and the result is {} -- with
+    `refined`, {"gmw": {}} -- which is what the reference's `--test` / `--test_all` leave behind for the upload."""
+    logger = logging.getLogger("dcd_amd.inference")
+    predict_folder = os.path.join(output_folder, "data")
+    labelled = getattr(files, "has_labels", True)
+    results = {}
+    if labelled:
+        dt_annos = kitti_annos.read_annos(predict_folder, ids)
+        gt_annos = kitti_annos.read_annos(os.path.join(files.root, "label_2"), ids)
+        for metric in metrics:
+            text, results[metric] = kitti_ap.official_eval(gt_annos, dt_annos, list(files.classes), metric=metric, device=device)
+            logger.info("%s\n%s", metric, text)
+    else:
+        missing = [i for i in ids if not os.path.isfile(os.path.join(predict_folder, i + ".txt"))]
+        if missing:
+            raise RuntimeError("the pass left no result file for %d of %d ids (first: %s)" % (len(missing), len(ids), missing[0]))
+        logger.info("%d result files in %s; the split has no labels, nothing is scored", len(ids), predict_folder)
+    if refined is not None:
+        from dcd_amd.gmw.inference import write_results, writer_fields
+        rows, host_ids, pred_location = refined
+        result_dir = write_results(writer_fields(rows, host_ids), pred_location, os.path.join(output_folder, "kitti_results_for_eval"), ids)
         results["gmw"] = {}
-        for metric in metrics:                                         # class 0, "Car": the one name GMW's files carry
-            text, results["gmw"][metric] = kitti_ap.official_eval(gt_annos, refined, 0, metric=metric, device=pipeline.device)
-            logger.info("GMW %s\n%s", metric, text)
+        if labelled:
+            refined_annos = kitti_annos.read_annos(result_dir, ids)
+            for metric in metrics:                                     # class 0, "Car": the one name GMW's files carry
+                text, results["gmw"][metric] = kitti_ap.official_eval(gt_annos, refined_annos, 0, metric=metric, device=device)
+                logger.info("GMW %s\n%s", metric, text)
     return results
 
 
@@ -201,8 +229,9 @@ def main(argv=None):
     from dcd_amd.engine.train import resume
     from dcd_amd.model.detector import KeypointDetector
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib")
-    ap.add_argument("--split", default="val")
+    ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib, kpts_ann (for --split test: "
+                    "ImageSets, image_2, calib)")
+    ap.add_argument("--split", default="val", help="ImageSets/<split>.txt; 'test' is the split without labels: written, not scored")
     ap.add_argument("--ckpt", required=True)
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--batch", type=int, default=1, help="images per model call (1: the one-image loop)")

@@ -389,7 +389,8 @@ def main(argv=None):
     from dcd_amd.engine.trainer import build_optimizer, build_scheduler
     from dcd_amd.model.detector import KeypointDetector
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib, kpts_ann")
+    ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib, kpts_ann (and image_3 for "
+                    "`DATASETS.USE_RIGHT_IMAGE True`, which trains on both cameras' views)")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--batch", type=int, default=None, help="images per step on this GPU (default SOLVER.IMS_PER_BATCH / world size)")
     ap.add_argument("--seed", type=int, default=0)
