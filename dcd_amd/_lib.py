@@ -183,6 +183,8 @@ SIGNATURES = {
     "dcd_gmw_train_records_workspace_bytes": (c_size_t, [c_int] * 3),
     "dcd_gmw_train_records": (c_int, [c_void_p, c_void_p, ctypes.POINTER(RecordsArgs)] + [c_void_p] * 9 + [c_int] + [c_void_p] * 8
                               + [c_int, c_int, c_void_p, c_size_t]),
+    "dcd_depth_estimates": (c_int, [c_void_p] * 8 + [ctypes.POINTER(DecodeArgs), c_void_p]),
+    "dcd_depth_accumulate": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), c_int, c_int, c_void_p, c_void_p]),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

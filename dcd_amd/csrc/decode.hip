@@ -14,7 +14,7 @@
 
 namespace {
 
-constexpr int DECODE_MAXK = 128;
+constexpr int DECODE_MAXK = DD_LANES;      // K and nk: the sizes dd_args_ok lets through
 
 __global__ __launch_bounds__(DD_LANES) void decode_detections(const float *__restrict__ vectors, const float *__restrict__ scores,
                                                               const float *__restrict__ classes, const float *__restrict__ ys,
@@ -59,16 +59,6 @@ __global__ __launch_bounds__(DD_LANES) void decode_detections(const float *__res
     if (tid == 0) dd_finish(a, h, tab, s_part[0], rows + (size_t)n * 14, aux + (size_t)n * 4);
 }
 
-bool channels_ok(const dcd_decode_args &a)
-{
-    const int start[11] = {a.ch_box2d, a.ch_offset, a.ch_corner, a.ch_corner_unc, a.ch_dims, a.ch_ori_cls, a.ch_ori_off, a.ch_depth,
-                           a.ch_depth_unc, a.ch_kpts2d, a.ch_kpts3d};
-    const int width[11] = {4, 2, 20, 3, 3, 2 * a.n_bins, 2 * a.n_bins, 1, 1, 2 * a.nk, 3 * a.nk};
-    for (int i = 0; i < 11; ++i)
-        if (start[i] < 0 || start[i] > a.C - width[i]) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int dcd_decode_detections(void *stream_, const float *vectors, const float *scores, const float *classes, const float *ys,
@@ -79,13 +69,7 @@ extern "C" int dcd_decode_detections(void *stream_, const float *vectors, const 
     const dcd_decode_args a = *args;
     if (!vectors || !scores || !classes || !ys || !xs || !image_table || !rows || !aux) return DCD_ERR_BAD_ARG;
     if (a.records && (!kpts2d || !kpts3d)) return DCD_ERR_BAD_ARG;
-    if (a.B < 1 || a.K < 1 || a.K > DECODE_MAXK || a.nk < 2 || a.nk > DECODE_MAXK || a.C < 1) return DCD_ERR_BAD_ARG;
-    if ((int64_t)a.B * a.K > 0x7fffffffLL) return DCD_ERR_BAD_ARG;
-    if (a.n_bins < 1 || a.n_bins > 4 || a.num_classes < 1 || a.num_classes > DCD_DECODE_MAX_CLASSES) return DCD_ERR_BAD_ARG;
-    if (a.orientation != DCD_DECODE_ORI_MULTIBIN) return DCD_ERR_BAD_ARG;
-    if (a.dim_mode < DCD_DECODE_DIM_NONE || a.dim_mode > DCD_DECODE_DIM_LINEAR) return DCD_ERR_BAD_ARG;
-    if (a.depth_mode < DCD_DECODE_DEPTH_INV_SIGMOID || a.depth_mode > DCD_DECODE_DEPTH_LINEAR) return DCD_ERR_BAD_ARG;
-    if (!channels_ok(a)) return DCD_ERR_BAD_ARG;
+    if (!dd_args_ok(a)) return DCD_ERR_BAD_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(decode_detections, dim3((unsigned)(a.B * a.K)), dim3(DD_LANES), 0, stream, vectors, scores, classes, ys, xs,
                        image_table, a, rows, aux, kpts2d, kpts3d);

@@ -62,6 +62,12 @@ struct DdHead {
     float roty, alpha;
 };
 
+// The four depth estimates of stages 3-4 and their sigmas of stage 5, in the fusion's order: 0 direct depth, 1 centre line,
+// 2 / 3 the corner groups.  The decode keeps them to itself; the depth report (depth_report_math.h) asks for them.
+struct DdDepths {
+    float depth[4], sigma[4];
+};
+
 // (centre + offset) * down_ratio - pad, back-projected at `depth` (decode_location_flatten, anno_encoder.py:147-161)
 DD_HD void dd_location(const dcd_decode_args &a, const DdHead &h, const float *tab, float depth, float *loc)
 {
@@ -76,7 +82,9 @@ DD_HD void dd_location(const dcd_decode_args &a, const DdHead &h, const float *t
 }
 
 // Stages 1-8 (detector_infer.py:104-180).  vec: the candidate's C head outputs; tab: its image's row of the table.
-DD_HD DdHead dd_head(const dcd_decode_args &a, const float *vec, float score, float cls, float y, float x, const float *tab)
+// est: where the four depths and sigmas go as well, or null.
+DD_HD DdHead dd_head(const dcd_decode_args &a, const float *vec, float score, float cls, float y, float x, const float *tab,
+                     DdDepths *est = nullptr)
 {
     DdHead h;
     h.cls = cls;
@@ -109,7 +117,8 @@ DD_HD DdHead dd_head(const dcd_decode_args &a, const float *vec, float score, fl
     }
 
     // 3. direct depth (decode_depth, anno_encoder.py:130-145)
-    float depths[4], sigma[4];
+    DdDepths four;
+    float *depths = four.depth, *sigma = four.sigma;
     {
         const float d = vec[a.ch_depth];
         float z;
@@ -179,6 +188,7 @@ DD_HD DdHead dd_head(const dcd_decode_args &a, const float *vec, float score, fl
         h.roty = dd_wrap(ori + ray);
         h.alpha = dd_wrap(ori);
     }
+    if (est) *est = four;
     return h;
 }
 
@@ -227,13 +237,19 @@ DD_HD float dd_pair_partial(int lane, int K, const float *vn, const float *Y, co
     return acc;
 }
 
+// the edge depth inference reports: the mean over all nk (nk - 1) / 2 pairs of the tree's sum of the lanes' partials
+DD_HD float dd_edge_depth(const dcd_decode_args &a, float pair_sum)
+{
+    const int npairs = a.nk * (a.nk - 1) / 2;
+    return pair_sum / (float)npairs;
+}
+
 // 11-14. the final location at the edge depth (the mean over all pairs), the (h, w, l) dimensions, the confidence and
 //        the 14-float row [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, roty, score]; aux = raw score, depth error,
 //        confidence, arg-max index.
 DD_HD void dd_finish(const dcd_decode_args &a, const DdHead &h, const float *tab, float pair_sum, float *row, float *aux)
 {
-    const int npairs = a.nk * (a.nk - 1) / 2;
-    const float edge_depth = pair_sum / (float)npairs;
+    const float edge_depth = dd_edge_depth(a, pair_sum);
     float loc[3];
     dd_location(a, h, tab, edge_depth, loc);
     loc[1] += h.dims[1] / 2.f;
@@ -256,4 +272,22 @@ DD_HD void dd_finish(const dcd_decode_args &a, const DdHead &h, const float *tab
     aux[1] = h.depth_error;
     aux[2] = conf;
     aux[3] = (float)h.best;
+}
+
+// What the launchers of decode.hip and depth_report.hip accept of a `dcd_decode_args` (host code): the sizes the kernels' LDS
+// arrays hold, the modes the header implements, every head inside a row of C channels.
+inline bool dd_args_ok(const dcd_decode_args &a)
+{
+    if (a.B < 1 || a.K < 1 || a.K > DD_LANES || a.nk < 2 || a.nk > DD_LANES || a.C < 1) return false;
+    if ((int64_t)a.B * a.K > 0x7fffffffLL) return false;
+    if (a.n_bins < 1 || a.n_bins > 4 || a.num_classes < 1 || a.num_classes > DCD_DECODE_MAX_CLASSES) return false;
+    if (a.orientation != DCD_DECODE_ORI_MULTIBIN) return false;
+    if (a.dim_mode < DCD_DECODE_DIM_NONE || a.dim_mode > DCD_DECODE_DIM_LINEAR) return false;
+    if (a.depth_mode < DCD_DECODE_DEPTH_INV_SIGMOID || a.depth_mode > DCD_DECODE_DEPTH_LINEAR) return false;
+    const int start[11] = {a.ch_box2d, a.ch_offset, a.ch_corner, a.ch_corner_unc, a.ch_dims, a.ch_ori_cls, a.ch_ori_off, a.ch_depth,
+                           a.ch_depth_unc, a.ch_kpts2d, a.ch_kpts3d};
+    const int width[11] = {4, 2, 20, 3, 3, 2 * a.n_bins, 2 * a.n_bins, 1, 1, 2 * a.nk, 3 * a.nk};
+    for (int i = 0; i < 11; ++i)
+        if (start[i] < 0 || start[i] > a.C - width[i]) return false;
+    return true;
 }

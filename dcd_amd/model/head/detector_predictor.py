@@ -334,12 +334,46 @@ class _predictor(nn.Module):
         from dcd_amd.model.layers.utils import select_topk
         feature_cls = self.class_head[:-1](features)
         output_cls = self.class_head[-1](feature_cls)
-        b, _, h, w = feature_cls.shape
+        b = feature_cls.shape[0]
         if self.enable_edge_fusion:
             output_cls = self._edge_fusion_cls(feature_cls, output_cls, targets)
         heat = sigmoid_hm(output_cls).float()
         topk = select_topk(heat, K=self.max_detection, fuse_nms=True)                 # scores, cell index, classes, ys, xs: (B, K) each
-        centers_lin = topk[1].long().view(b, -1)
+        reg_pois = self._heads_at(features, targets, topk[1].long().view(b, -1))
+        return {'cls': heat, 'reg': None, 'reg_pois': reg_pois, 'topk': topk}
+
+    def _sparse_eval_refusal(self, features):
+        """Why the heads cannot be evaluated at chosen cells on this input, or None: the conditions `forward` puts before
+        `_forward_sparse_eval`."""
+        if self.training:
+            return "the predictor is in training mode"
+        if self.deeper_head:
+            return "MODEL.HEAD.DEEPER_HEAD puts a dense stem in front of the trunks"
+        if not features.is_cuda or features.dtype != torch.float32:
+            return "the features are %s on %s (float32 on the GPU only)" % (features.dtype, features.device)
+        if torch.is_grad_enabled():
+            return "gradients are enabled (call it under torch.no_grad())"
+        if not self._head_rows_ok():
+            return "the output layers are not the 1x1 convolutions ops.head_rows takes"
+        if not trunk_moments.frozen(self.reg_features, features):
+            return "the trunks are not 3x3 conv + BatchNorm in eval mode + ReLU"
+        if self.output_width != features.shape[3] or self.output_height != features.shape[2]:
+            return "the feature map is %d x %d, the configured output %d x %d" % (features.shape[3], features.shape[2],
+                                                                                 self.output_width, self.output_height)
+        return None
+
+    def heads_at(self, features, targets, centers_lin):
+        """The regression heads at chosen cells: features (B, C, H, W) of the backbone, centers_lin (B, M) linear cell indices
+        y * W + x -> `reg_pois` (B, M, C), the edge-fusion term of the 3d_offset head included: what the dense map holds at those
+        cells, from the frozen-BN trunks and one `ops.head_rows` launch.  It is the second half of the sparse evaluation path and
+        has its preconditions; NotImplementedError names the one that fails."""
+        why = self._sparse_eval_refusal(features)
+        if why is not None:
+            raise NotImplementedError("heads_at: " + why)
+        return self._heads_at(features, targets, centers_lin.long().view(features.shape[0], -1))
+
+    def _heads_at(self, features, targets, centers_lin):
+        b, w = features.shape[0], features.shape[3]
         M = centers_lin.shape[1]
         extra = None
         if self.enable_edge_fusion:
@@ -358,15 +392,13 @@ class _predictor(nn.Module):
             ch0 = sum(hd.out_channels for _, hd in heads[:first])
             edge = self._edge_fusion_at_pois(at_extra.transpose(1, 2), edge_lin, edge_valid, centers_lin)
             reg_pois = reg_pois + F.pad(edge, (ch0, reg_pois.shape[2] - ch0 - edge.shape[2]))
-        return {'cls': heat, 'reg': None, 'reg_pois': reg_pois.float(), 'topk': topk}
+        return reg_pois.float()
 
     def forward(self, features, targets):
         if (self.training and self.sparse_training_heads and targets is not None and self.exact_edge_gather
                 and self.output_width == features.shape[3] and self.output_height == features.shape[2]):
             return self._forward_sparse(features, targets)
-        if (not self.training and self.sparse_eval_heads and not self.deeper_head and features.is_cuda and features.dtype == torch.float32
-                and not torch.is_grad_enabled() and self._head_rows_ok() and trunk_moments.frozen(self.reg_features, features)
-                and self.output_width == features.shape[3] and self.output_height == features.shape[2]):
+        if self.sparse_eval_heads and self._sparse_eval_refusal(features) is None:
             return self._forward_sparse_eval(features, targets)
         feat_cls_in = self.cls_head_pre(features) if self.deeper_head else features
         feature_cls = self.class_head[:-1](feat_cls_in)

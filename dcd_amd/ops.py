@@ -2013,3 +2013,63 @@ def decode_detections(vectors, topk, image_table, spec, records=False):
                                  xs.data_ptr(), table.data_ptr(), a, rows.data_ptr(), aux.data_ptr(), _lib.ptr(k2), _lib.ptr(k3))
     _lib.check(st, "dcd_decode_detections")
     return rows, aux, k2, k3
+
+
+DEPTH_METHODS = ("direct", "kpt_center", "kpt_02", "kpt_13", "soft", "hard", "mean", "edges", "oracle", "gmw")
+DEPTH_ROW = 3 + len(DEPTH_METHODS)     # valid, class, gt_z, the methods
+DEPTH_STATS = 5                        # count, sum |e|, sum e, sum e^2, non-finite estimates
+DEPTH_MAX_BINS = 16
+
+
+def depth_estimates(vectors, ys, xs, classes, gt_z, valid, image_table, spec):
+    """Every depth estimate of a batch of labelled objects in ONE launch: vectors (B, M, C) head outputs at the objects' cells,
+    ys / xs / classes / gt_z / valid (B, M) (any numeric dtype; valid: 0 = empty slot), image_table (B, 16) as for
+    `decode_detections`, spec of `PostProcessor.decode_spec`.  Returns est (B M, 13) = [valid, class, gt_z, the ten
+    `DEPTH_METHODS`]; the `gmw` column is NaN (the caller's), an empty slot's row is all zeros.  No host synchronisation.
+    A configuration the kernel does not cover gives `DcdHipError` (status 1) without a launch."""
+    _lib.require_cuda(vectors, ys, xs, classes, gt_z, valid, image_table)
+    if vectors.dim() != 3:
+        raise ValueError("depth_estimates: vectors is %s, expected (B, M, C)" % (tuple(vectors.shape),))
+    B, M, C = vectors.shape
+    vec, table = _f32c(vectors).reshape(B * M, C), _f32c(image_table)
+    if tuple(table.shape) != (B, DECODE_TABLE):
+        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
+    per_slot = [ys, xs, classes, gt_z, valid]
+    if any(t.numel() != B * M for t in per_slot):
+        raise ValueError("depth_estimates: ys, xs, classes, gt_z and valid hold one value per slot (%d x %d)" % (B, M))
+    ys, xs, classes, gt_z = (_f32c(t) for t in per_slot[:4])
+    valid = _typed(valid, torch.uint8)
+    a = decode_args(spec, B, M, C)
+    est = torch.empty((B * M, DEPTH_ROW), dtype=torch.float32, device=vec.device)
+    st = _lib.lib().dcd_depth_estimates(_lib.stream_of(vec), vec.data_ptr(), ys.data_ptr(), xs.data_ptr(), classes.data_ptr(),
+                                        gt_z.data_ptr(), valid.data_ptr(), table.data_ptr(), a, est.data_ptr())
+    _lib.check(st, "dcd_depth_estimates")
+    return est
+
+
+def depth_tables(num_classes, n_bins, device):
+    """Zeroed running tables for `depth_accumulate`: (table (num_classes, n_bins, 10, 5) float64, outside (num_classes) int64)."""
+    return (torch.zeros((num_classes, n_bins, len(DEPTH_METHODS), DEPTH_STATS), dtype=torch.float64, device=device),
+            torch.zeros((num_classes,), dtype=torch.int64, device=device))
+
+
+def depth_accumulate(est, edges, table, outside):
+    """The rows of `depth_estimates` booked into the running tables of `depth_tables`, in place and in one launch: an object of
+    class c falls in bin i when edges[i] <= gt_z < edges[i + 1] (edges: n_bins + 1 increasing numbers on the host) and adds
+    e = d - gt_z, in double, to the stats [count, sum |e|, sum e, sum e^2] of cell (c, i, method); a non-finite estimate raises the
+    cell's fifth stat instead; an object in no bin counts in outside[c] only.  Every cell adds its objects in slot order, so the
+    tables have the same bits however a split is cut into calls.  No host synchronisation."""
+    _lib.require_cuda(est, table, outside)
+    edges = [float(e) for e in edges]
+    n_bins = len(edges) - 1
+    if est.dim() != 2 or est.shape[1] != DEPTH_ROW or est.dtype != torch.float32 or not est.is_contiguous():
+        raise ValueError("depth_accumulate: est is %s %s, expected contiguous float32 (n, %d)" % (est.dtype, tuple(est.shape), DEPTH_ROW))
+    num_classes = int(outside.shape[0]) if outside.dim() == 1 else -1
+    if (table.dtype != torch.float64 or outside.dtype != torch.int64 or not table.is_contiguous() or not outside.is_contiguous()
+            or tuple(table.shape) != (num_classes, n_bins, len(DEPTH_METHODS), DEPTH_STATS)):
+        raise ValueError("depth_accumulate: table %s %s / outside %s %s do not fit %d bins (see depth_tables)"
+                         % (table.dtype, tuple(table.shape), outside.dtype, tuple(outside.shape), n_bins))
+    c_edges = (_lib.c_float * max(len(edges), 1))(*edges)
+    st = _lib.lib().dcd_depth_accumulate(_lib.stream_of(est), est.data_ptr(), int(est.shape[0]), c_edges, n_bins, num_classes,
+                                         table.data_ptr(), outside.data_ptr())
+    _lib.check(st, "dcd_depth_accumulate")

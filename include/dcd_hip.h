@@ -925,6 +925,48 @@ int dcd_gmw_train_records(void *stream, const float *reg_pois, const dcd_records
                           float *kpts_2d, float *kpts_3d, float *pred_rot, float *gt_location, float *pred_location, int32_t *image,
                           int32_t *cursor, int32_t *per_call, int call, int n_calls, void *workspace, size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * The depth report (csrc/depth_report.hip, arithmetic in csrc/depth_report_math.h on top of csrc/decode_math.h): every depth
+ * estimate the decode forms on its way to a row, for labelled objects, and the error of each against the label, booked by
+ * class and range.
+ *
+ * dcd_depth_estimates: one launch, one workgroup per object slot, B * M slots (args->B images, args->K = M slots each; the
+ * struct is the decode's, `uncertainty_as_conf` and `records` are not read).
+ *   vectors      (B M, C) fp32: the regression heads at the objects' centre cells
+ *   ys, xs, classes   (B M) fp32: the cell and the class, as dcd_decode_detections takes them
+ *   gt_z         (B M) fp32: the label's depth;  valid (B M) u8: 0 = empty slot
+ *   image_table  (B, 16) fp32 as for dcd_decode_detections; every object uses its own image's row
+ *   est          (B M, 13): valid (1 or 0), class, gt_z, then the 10 methods
+ *                  0 direct      the direct depth head             5 hard    the estimate with the smallest sigma
+ *                  1 kpt_center  key-point depth, centre line      6 mean    plain mean of 0-3
+ *                  2 kpt_02      key-point depth, corners 0/2      7 edges   mean over all nk (nk - 1) / 2 pairs minus P[2][3]:
+ *                  3 kpt_13      key-point depth, corners 1/3                the z dcd_decode_detections reports, same bits
+ *                  4 soft        inverse-sigma weighted mean       8 oracle  the one of 0-3 closest to gt_z, first on a tie
+ *                                                                  9 gmw     NaN: the caller's column
+ * An empty slot's row is thirteen zeros and its vector is never read.  A row depends on its own slot only; a non-finite vector
+ * gives non-finite estimates in that row and touches no other (method 7 alone can stay finite: the edge solver's clamp drops a
+ * NaN, as in the decode).  Fixed-order sums, no atomics: two calls give the same bits.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer and for everything dcd_decode_detections refuses (M > 128,
+ * nk > 128, head-axis orientation, ...).
+ *
+ * dcd_depth_accumulate: adds the rows of one batch to running tables in device memory, one launch.
+ *   est          (n_slots, 13) as above, column 12 filled by the caller or left NaN
+ *   edges        n_bins + 1 floats ON THE HOST, read during the call: an object falls in bin i when edges[i] <= gt_z < edges[i + 1]
+ *   table        (num_classes, n_bins, 10, 5) fp64, zeroed by the caller before the first call: per cell the count of finite
+ *                estimates, sum |e|, sum e, sum e^2 and the count of non-finite estimates, e = d - gt_z in double
+ *   outside      (num_classes) i64: objects whose gt_z is below edges[0], at or above edges[n_bins], or not finite; they are
+ *                booked nowhere else.  A row whose class is outside [0, num_classes) is booked nowhere at all.
+ * One thread per cell walks the rows in slot order and adds its own to its five doubles: no floating-point atomics, no
+ * reduction between threads.  A cell's sums are therefore the same sequence of additions whether a split arrives in one call or
+ * in many, and two passes agree bit for bit.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer, n_slots < 0, n_bins outside 1 .. 16, num_classes outside
+ * 1 .. 8, or edges that are not finite and strictly increasing.  n_slots = 0 is DCD_OK and does nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_depth_estimates(void *stream, const float *vectors, const float *ys, const float *xs, const float *classes,
+                        const float *gt_z, const uint8_t *valid, const float *image_table, const dcd_decode_args *args, float *est);
+int dcd_depth_accumulate(void *stream, const float *est, int n_slots, const float *edges, int n_bins, int num_classes,
+                         double *table, int64_t *outside);
+
 #ifdef __cplusplus
 }
 #endif
