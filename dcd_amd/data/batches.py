@@ -27,7 +27,7 @@ next to overwrite, while the step still reads it.
 Evaluation over a split has a FINITE plan of its own: `EvalPlan(size, batch_size)` gives batch k = images
 [k B, min((k + 1) B, size)) in file order -- the last batch may be short, nothing wraps around, nothing flips -- and
 `EvalBatches(files, pipeline, batch_size, workers=None)` decodes them in a thread pool; `EvalPrefetcher` is the `Prefetcher` that
-stops at the last batch."""
+stops at the last batch; `eval_batches(files, pipeline, batch_size, workers=None)` is the two together, as the passes walk them."""
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -203,3 +203,27 @@ class EvalPrefetcher(Prefetcher):
     def _produce(self, k):
         if k < self.source.num_batches:
             super()._produce(k)
+
+
+class eval_batches:
+    """A split in evaluation order, one batch ahead: `EvalBatches` behind an `EvalPrefetcher` on the pipeline's device.
+
+        with eval_batches(files, pipeline, batch_size, workers) as walk:
+            for k, indices, images, targets in walk:          # k = 0 .. num_batches - 1; indices: the batch's image numbers
+
+    Leaving the `with` block, by its end or by an exception, shuts the thread pool down."""
+
+    def __init__(self, files, pipeline, batch_size, workers=None):
+        self.source = EvalBatches(files, pipeline, batch_size, workers)
+        self._batches = EvalPrefetcher(self.source, pipeline.device)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.source.close()
+
+    def __iter__(self):
+        for k in range(self.source.num_batches):
+            images, targets = self._batches.get(k)
+            yield k, self.source.plan(k)[0], images, targets

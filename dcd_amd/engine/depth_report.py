@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from dcd_amd import ops
+from dcd_amd.engine.passes import load_detector, load_gmw, parse_overrides, restored_modes
 from dcd_amd.structures.params_3d import stack_field
 
 DEFAULT_EDGES = (0, 10, 20, 30, 40, 50, 60, 80)
@@ -43,23 +44,11 @@ class _GmwColumn:
     slots in groups of `cap` through `ops.gmw_pack_records` and `refine_packed`."""
 
     def __init__(self, gmw, device, cap, nk):
-        from dcd_amd.gmw.inference import NUM_KPTS
-        if nk != NUM_KPTS or int(gmw.num_kpts) != NUM_KPTS:
-            raise ValueError("depth_report(gmw=...): %d key points (model: %d); GMW's pair tables are for %d" % (nk, int(gmw.num_kpts), NUM_KPTS))
-        if cap < 1:
-            raise ValueError("gmw batch %d" % cap)
-        if next(gmw.parameters()).dtype != torch.float32:
-            raise ValueError("depth_report(gmw=...) runs in float32 (the model is %s)" % next(gmw.parameters()).dtype)
-        self.gmw, self.cap = gmw, int(cap)
-        P = nk * (nk - 1) // 2
-        self.pair_i = gmw.pair_i.to(device=device, dtype=torch.int32).contiguous()
-        self.pair_j = gmw.pair_j.to(device=device, dtype=torch.int32).contiguous()
-        shapes = ((4, P), (6, P), (nk, 2), (nk, 3), (1,), (3,), (3,))        # e4, e6, k2, k3, rot, loc, dim
-        self.buffers = [torch.zeros((self.cap,) + s, dtype=torch.float32, device=device) for s in shapes]
+        from dcd_amd.gmw.inference import PackBuffers
+        self.packs = PackBuffers(gmw, device, cap, nk, "depth_report(gmw=...)")
         self.src = torch.arange(8 * MAX_SLOTS, dtype=torch.int32, device=device)
 
     def __call__(self, vectors, lin, classes, ys, xs, table, spec):
-        from dcd_amd.gmw.inference import refine_packed
         B, M = lin.shape
         n = B * M
         if self.src.numel() < n:
@@ -67,10 +56,11 @@ class _GmwColumn:
         topk = (torch.zeros((B, M), dtype=torch.float32, device=lin.device), lin, classes, ys, xs)
         rows, _, k2, k3 = ops.decode_detections(vectors, topk, table, spec, records=True)
         z = torch.empty(n, dtype=torch.float32, device=lin.device)
-        for s in range(0, n, self.cap):
-            count = min(self.cap, n - s)
-            ops.gmw_pack_records(rows, k2, k3, self.src[s:s + count], 0, self.pair_i, self.pair_j, *self.buffers)
-            z[s:s + count] = refine_packed(self.gmw, *(b[:count] for b in self.buffers))[0]
+        cap = self.packs.cap
+        for s in range(0, n, cap):
+            count = min(cap, n - s)
+            self.packs.pack(rows, k2, k3, self.src[s:s + count], 0)
+            z[s:s + count] = self.packs.refine(count)[0]
         return z
 
 
@@ -152,7 +142,7 @@ def depth_report(model, files, pipeline, batch_size=8, edges=DEFAULT_EDGES, gmw=
     per_object=True adds result["est"] (N, 13) -- every slot's row [valid, class, gt_z, the methods] in split order, one bulk copy --
     and result["img_ids"], each row's image id.
     Raises ValueError for a split without labels, NotImplementedError for a configuration the kernels do not cover."""
-    from dcd_amd.data.batches import EvalBatches, EvalPrefetcher
+    from dcd_amd.data.batches import eval_batches
     if not getattr(files, "has_labels", True):
         raise ValueError("depth_report needs a labelled split: %r has no labels to measure against" % getattr(files, "split", files))
     if pipeline.is_train:
@@ -173,35 +163,23 @@ def depth_report(model, files, pipeline, batch_size=8, edges=DEFAULT_EDGES, gmw=
     classes = [names.get(c, "class %d" % c) for c in range(len(spec["dim_mean"]))]
     device = pipeline.device
     table, outside = ops.depth_tables(len(classes), n_bins, device)
-    was_training = model.training
-    model.eval()
-    gmw_column, gmw_training = None, None
+    gmw_column = None
     kept, ids = [], []
-    try:
-        with torch.no_grad():
-            if gmw is not None:
-                gmw_training = gmw.training
-                gmw.eval()
-                gmw_column = _GmwColumn(gmw, device, gmw_batch, spec["nk"])
-            source = EvalBatches(files, pipeline, batch_size, workers)
-            batches = EvalPrefetcher(source, device)
-            try:
-                for k in range(source.num_batches):
-                    images, targets = batches.get(k)
-                    est = report_batch(model, images, targets, spec, edges, table, outside, gmw_column, backbone_batch)
-                    if per_object:
-                        kept.append(est)
-                        slots = est.shape[0] // len(targets)
-                        ids.extend(files.img_id(i) for i in source.plan(k)[0] for _ in range(slots))
-            finally:
-                source.close()
-            # the one copy: the sums and, as the same 8-byte words, the counters
-            flat = torch.cat((table.reshape(-1), outside.view(torch.float64))).cpu().numpy()
-            est_host = torch.cat(kept).cpu().numpy() if kept else np.zeros((0, ops.DEPTH_ROW), np.float32)
-    finally:
-        model.train(was_training)
-        if gmw is not None and gmw_training is not None:
-            gmw.train(gmw_training)
+    with restored_modes(model, gmw), torch.no_grad():
+        model.eval()
+        if gmw is not None:
+            gmw.eval()
+            gmw_column = _GmwColumn(gmw, device, gmw_batch, spec["nk"])
+        with eval_batches(files, pipeline, batch_size, workers) as walk:
+            for k, indices, images, targets in walk:
+                est = report_batch(model, images, targets, spec, edges, table, outside, gmw_column, backbone_batch)
+                if per_object:
+                    kept.append(est)
+                    slots = est.shape[0] // len(targets)
+                    ids.extend(files.img_id(i) for i in indices for _ in range(slots))
+        # the one copy: the sums and, as the same 8-byte words, the counters
+        flat = torch.cat((table.reshape(-1), outside.view(torch.float64))).cpu().numpy()
+        est_host = torch.cat(kept).cpu().numpy() if kept else np.zeros((0, ops.DEPTH_ROW), np.float32)
     result = summarise(flat[:table.numel()].reshape(tuple(table.shape)), flat[table.numel():].view(np.int64), edges, classes)
     if per_object:
         result["est"], result["img_ids"] = est_host, ids
@@ -215,13 +193,10 @@ def main(argv=None):
     [--edges 0 10 ...] [--output-dir DIR] [KEY VALUE ...]`: the depth report of a saved checkpoint (a file, or a directory with
     `last_checkpoint`) on one GPU."""
     import argparse
-    import ast
     import json
     from dcd_amd.config import get_cfg
     from dcd_amd.data.input_pipeline import DeviceInputPipeline
     from dcd_amd.data.kitti_files import KittiFiles
-    from dcd_amd.engine.train import resume
-    from dcd_amd.model.detector import KeypointDetector
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib, kpts_ann")
     ap.add_argument("--split", default="val", help="ImageSets/<split>.txt; it must have labels")
@@ -250,23 +225,10 @@ def main(argv=None):
     if args.edges is not None:
         n = next((i for i, s in enumerate(args.edges) if not is_number(s)), len(args.edges))
         edges, args.opts = [float(s) for s in args.edges[:n]], args.edges[n:] + args.opts
-    opts = []
-    for k, v in zip(args.opts[0::2], args.opts[1::2]):
-        try:
-            v = ast.literal_eval(v)
-        except (ValueError, SyntaxError):
-            pass
-        opts += [k, v]
-    cfg = get_cfg(opts=opts)
+    cfg = get_cfg(opts=parse_overrides(args.opts))
     device = torch.device("cuda", torch.cuda.current_device())
-    model = KeypointDetector(cfg).to(device)
-    resume(args.ckpt, model)
-    gmw = None
-    if args.gmw_ckpt:
-        from dcd_amd.gmw import GMW
-        gmw = GMW().to(device)
-        state = torch.load(args.gmw_ckpt, map_location="cpu", weights_only=False)["state_dict"]
-        gmw.load_state_dict({k.replace("module.", ""): v for k, v in state.items()})
+    model, _ = load_detector(cfg, args.ckpt, device)
+    gmw = load_gmw(args.gmw_ckpt, device) if args.gmw_ckpt else None
     files = KittiFiles(args.root, args.split, cfg, is_train=False)
     pipeline = DeviceInputPipeline(cfg, device, is_train=False)
     text, result = depth_report(model, files, pipeline, batch_size=args.batch, edges=edges, gmw=gmw, gmw_batch=args.gmw_batch,

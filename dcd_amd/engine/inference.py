@@ -28,6 +28,7 @@ import os
 import numpy as np
 import torch
 
+from dcd_amd.engine.passes import load_detector, load_gmw, parse_overrides, restored_modes
 from dcd_amd.eval import kitti_annos, kitti_ap
 
 
@@ -58,15 +59,12 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     leaves the key points on the device, every batch's kept rows are handed to it (`refiner.add`, a batch late, with the host
     rows appended to `refiner.host_rows` / `refiner.host_ids` for the writer), and the key points go to the host only with
     `want_records`."""
-    from dcd_amd.data.batches import EvalBatches, EvalPrefetcher
+    from dcd_amd.data.batches import eval_batches
     pp, predictor = model.heads.post_processor, model.heads.predictor
-    spec = pp.decode_spec()                                            # refuses here, not in the middle of the split
-    device = pipeline.device
+    spec = pp.decode_spec()                                            # refuses here, before the walker and its threads exist
     K, nk = pp.max_detection, spec["nk"]
     width = 18 + (nk * 5 if want_records else 0)                       # rows (14) | aux (4) | kpts_2d | kpts_3d
     threshold = pp.det_threshold
-    source = EvalBatches(files, pipeline, batch_size, workers)
-    batches = EvalPrefetcher(source, device)
     slots = [torch.empty((batch_size * K, width), dtype=torch.float32).pin_memory() for _ in range(2)]
     views = [s.numpy() for s in slots]
     events = [torch.cuda.Event() for _ in range(2)]
@@ -94,24 +92,23 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     sparse_before = predictor.sparse_eval_heads
     predictor.sparse_eval_heads = True
     try:
-        pending = None
-        for k in range(source.num_batches):
-            images, targets = batches.get(k)
-            feats = model.backbone(images)
-            preds = predictor(feats, targets)
-            rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records or refiner is not None)
-            n = rows.shape[0]
-            parts = [rows, aux] + ([recs[0].reshape(n, nk * 2), recs[1].reshape(n, nk * 3)] if want_records else [])
-            slots[k % 2][:n].copy_(torch.cat(parts, dim=1), non_blocking=True)
-            events[k % 2].record()
+        with eval_batches(files, pipeline, batch_size, workers) as walk:
+            pending = None
+            for k, indices, images, targets in walk:
+                feats = model.backbone(images)
+                preds = predictor(feats, targets)
+                rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records or refiner is not None)
+                n = rows.shape[0]
+                parts = [rows, aux] + ([recs[0].reshape(n, nk * 2), recs[1].reshape(n, nk * 3)] if want_records else [])
+                slots[k % 2][:n].copy_(torch.cat(parts, dim=1), non_blocking=True)
+                events[k % 2].record()
+                if pending is not None:
+                    finish(*pending)
+                pending = (k, [files.img_id(i) for i in indices], (rows, recs[0], recs[1]) if refiner is not None else None)
             if pending is not None:
                 finish(*pending)
-            pending = (k, [files.img_id(i) for i in source.plan(k)[0]], (rows, recs[0], recs[1]) if refiner is not None else None)
-        if pending is not None:
-            finish(*pending)
     finally:
         predictor.sparse_eval_heads = sparse_before
-        source.close()
     return infer_data
 
 
@@ -137,43 +134,36 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     predict_folder = os.path.join(output_folder, "data")
     os.makedirs(predict_folder, exist_ok=True)
     ids = [files.img_id(i) for i in range(len(files))]
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            batched = batch_size > 1 or gen_out_dir is not None or gmw is not None
-            refiner = None
-            if gmw is not None:
-                from dcd_amd.gmw.inference import RecordRefiner
-                gmw_training = gmw.training
-                gmw.eval()
-                refiner = RecordRefiner(gmw, pipeline.device, batch_size=gmw_batch, nk=model.heads.post_processor.extra_kpts_num + 10)
-            if batched:
-                try:
-                    infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
-                                               refiner)
-                    if gen_out_dir is not None:
-                        from dcd_amd.engine import gen_data
-                        gen_data.dump_gen_data_infer(infer_data, gen_out_dir)
-                except NotImplementedError as e:
-                    if gmw is not None:
-                        raise NotImplementedError("inference(gmw=...) needs the fused decode, which refuses this configuration: %s" % e)
-                    logger.info("batched evaluation is not available (%s): one image per call", e)
-                    batched = False
-                    if gen_out_dir is not None:
-                        from dcd_amd.engine.train import generate_infer_data
-                        generate_infer_data(model, files, pipeline, gen_out_dir)
-            if not batched:
-                for i, img_id in enumerate(ids):
-                    images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
-                    rows = model(images, targets)[0]
-                    kitti_annos.write_detections(rows, os.path.join(predict_folder, img_id + ".txt"))
-            if refiner is not None:
-                pred_location = refiner.finish()
-    finally:
-        model.train(was_training)
+    with restored_modes(model, gmw), torch.no_grad():
+        model.eval()
+        batched = batch_size > 1 or gen_out_dir is not None or gmw is not None
+        refiner = None
         if gmw is not None:
-            gmw.train(gmw_training)
+            from dcd_amd.gmw.inference import RecordRefiner
+            gmw.eval()
+            refiner = RecordRefiner(gmw, pipeline.device, batch_size=gmw_batch, nk=model.heads.post_processor.extra_kpts_num + 10)
+        if batched:
+            try:
+                infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
+                                           refiner)
+                if gen_out_dir is not None:
+                    from dcd_amd.engine import gen_data
+                    gen_data.dump_gen_data_infer(infer_data, gen_out_dir)
+            except NotImplementedError as e:
+                if gmw is not None:
+                    raise NotImplementedError("inference(gmw=...) needs the fused decode, which refuses this configuration: %s" % e)
+                logger.info("batched evaluation is not available (%s): one image per call", e)
+                batched = False
+                if gen_out_dir is not None:
+                    from dcd_amd.engine.train import generate_infer_data
+                    generate_infer_data(model, files, pipeline, gen_out_dir)
+        if not batched:
+            for i, img_id in enumerate(ids):
+                images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
+                rows = model(images, targets)[0]
+                kitti_annos.write_detections(rows, os.path.join(predict_folder, img_id + ".txt"))
+        if refiner is not None:
+            pred_location = refiner.finish()
     refined = None
     if refiner is not None:
         rows = np.concatenate(refiner.host_rows, 0) if refiner.host_rows else np.zeros((0, 14), np.float32)
@@ -221,13 +211,10 @@ def main(argv=None):
     """`python -m dcd_amd.engine.inference --root KITTI_DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
     [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
     import argparse
-    import ast
     import json
     from dcd_amd.config import get_cfg
     from dcd_amd.data.input_pipeline import DeviceInputPipeline
     from dcd_amd.data.kitti_files import KittiFiles
-    from dcd_amd.engine.train import resume
-    from dcd_amd.model.detector import KeypointDetector
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--root", required=True, help="KITTI directory: ImageSets, image_2, label_2, calib, kpts_ann (for --split test: "
                     "ImageSets, image_2, calib)")
@@ -243,23 +230,10 @@ def main(argv=None):
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
-    opts = []
-    for k, v in zip(args.opts[0::2], args.opts[1::2]):
-        try:
-            v = ast.literal_eval(v)
-        except (ValueError, SyntaxError):
-            pass
-        opts += [k, v]
-    cfg = get_cfg(opts=opts)
+    cfg = get_cfg(opts=parse_overrides(args.opts))
     device = torch.device("cuda", torch.cuda.current_device())
-    model = KeypointDetector(cfg).to(device)
-    resume(args.ckpt, model)
-    gmw = None
-    if args.gmw_ckpt:
-        from dcd_amd.gmw import GMW
-        gmw = GMW().to(device)
-        state = torch.load(args.gmw_ckpt, map_location="cpu", weights_only=False)["state_dict"]
-        gmw.load_state_dict({k.replace("module.", ""): v for k, v in state.items()})
+    model, _ = load_detector(cfg, args.ckpt, device)
+    gmw = load_gmw(args.gmw_ckpt, device) if args.gmw_ckpt else None
     files = KittiFiles(args.root, args.split, cfg, is_train=False)
     pipeline = DeviceInputPipeline(cfg, device, is_train=False)
     gen_out_dir = os.path.join(args.output_dir, "gen_data") if args.gen_data else None

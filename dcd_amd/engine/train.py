@@ -29,6 +29,7 @@ from collections import deque
 import torch
 
 from dcd_amd.engine import gen_data
+from dcd_amd.engine.passes import parse_overrides, restored_modes
 from dcd_amd.engine.trainer import checkpoint_state, load_checkpoint_state, step_schedulers, train_step
 from dcd_amd.utils import comm
 
@@ -173,20 +174,16 @@ def freeze_bn(model):
 
 def generate_infer_data(model, files, pipeline, out_dir):
     """`gen_data_infer.json` of the collection pass (DGDE/engine/inference.py:59-84): one image per model call."""
-    was_training = model.training
-    model.eval()
     infer_data = {}
-    try:
-        with torch.no_grad():
-            for i in range(len(files)):
-                img_id = files.img_id(i)
-                images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
-                feats = model.backbone(images)
-                preds = model.heads.predictor(feats, targets)
-                rows, _, vis, image_of = model.heads.post_processor.forward_batch(preds, targets, test=model.test, features=feats)
-                infer_data[img_id] = gen_data.infer_records_batch(rows, vis, image_of, 1)[0]
-    finally:
-        model.train(was_training)
+    with restored_modes(model), torch.no_grad():
+        model.eval()
+        for i in range(len(files)):
+            img_id = files.img_id(i)
+            images, targets = pipeline([files.frame(i)], [files.sample(i)], img_ids=[img_id])
+            feats = model.backbone(images)
+            preds = model.heads.predictor(feats, targets)
+            rows, _, vis, image_of = model.heads.post_processor.forward_batch(preds, targets, test=model.test, features=feats)
+            infer_data[img_id] = gen_data.infer_records_batch(rows, vis, image_of, 1)[0]
     return gen_data.dump_gen_data_infer(infer_data, out_dir)
 
 
@@ -256,16 +253,12 @@ def collect_gmw_records(model, batches, iterations, start=0, capacity=None, cfg=
             capacity = iterations * B * M
     collector = TrainRecordCollector(cfg, device, capacity, iterations)
     numbers = torch.tensor(rows, dtype=torch.int32).to(device)          # every iteration's image numbers, one copy before the loop
-    was_training = model.training
-    model.train()
-    freeze_bn(model)
-    try:
-        with torch.no_grad():
-            for it in range(iterations):
-                images, targets = batches.get(start + it)
-                collect_step(model, collector, images, targets, numbers[it])
-    finally:
-        model.train(was_training)
+    with restored_modes(model), torch.no_grad():
+        model.train()
+        freeze_bn(model)
+        for it in range(iterations):
+            images, targets = batches.get(start + it)
+            collect_step(model, collector, images, targets, numbers[it])
     records = collector.finish()
     records.collector = collector
     return records
@@ -380,7 +373,6 @@ def main(argv=None):
     """`python -m dcd_amd.engine.train --root KITTI_DIR --output-dir OUT [KEY VALUE ...]`: one process, one GPU (rank and world
     size are taken from the process group when one is initialised)."""
     import argparse
-    import ast
     from dcd_amd.config import get_cfg
     from dcd_amd.data.batches import Prefetcher, ResidentBatches, StreamingBatches
     from dcd_amd.data.input_pipeline import DeviceInputPipeline
@@ -402,14 +394,7 @@ def main(argv=None):
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
-    opts = []
-    for k, v in zip(args.opts[0::2], args.opts[1::2]):
-        try:
-            v = ast.literal_eval(v)
-        except (ValueError, SyntaxError):
-            pass
-        opts += [k, v]
-    cfg = get_cfg(opts=opts)
+    cfg = get_cfg(opts=parse_overrides(args.opts))
     device = torch.device("cuda", torch.cuda.current_device())
     rank, world = comm.get_rank(), comm.get_world_size()
     batch = args.batch if args.batch is not None else max(1, cfg.SOLVER.IMS_PER_BATCH // world)

@@ -20,7 +20,7 @@ import torch
 
 from dcd_amd import _lib
 from dcd_amd.model.layers.utils import Converter_key2channel
-from dcd_amd.structures.params_3d import stack_field
+from dcd_amd.structures.params_3d import _typed, stack_field
 from .data import KEYS, ResidentRecords
 
 TABLES = ("kpts_2d", "kpts_3d", "pred_rot", "gt_location", "pred_location")
@@ -64,14 +64,6 @@ def _entry(device):
         raise _lib.DcdHipError("dcd_amd.gmw.collect runs on the GPU only; there is no CPU path")
     L = _lib.lib()
     return L.dcd_gmw_train_records_workspace_bytes, L.dcd_gmw_train_records
-
-
-def _typed(t, dtype):
-    if t.dtype == torch.bool and dtype == torch.uint8:
-        t = t.view(torch.uint8)
-    elif t.dtype != dtype:
-        t = t.to(dtype)
-    return t.contiguous()
 
 
 def calib_rows(calibs):

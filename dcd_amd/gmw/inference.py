@@ -12,6 +12,8 @@ ray, `GMW_data` (main.py:123-215) rewrites the result files and calls the KITTI 
                     stock chain (`F.normalize`, the diagonal of `pairwise_l2_dist`, `compute_reg_loss`) in the model's dtype on
                     any device: what the tests measure against, and in float64 their reference;
   refine_packed     the body of that loop on device tensors that are already in the extractors' layout;
+  PackBuffers       a group of records in that layout on the device: the buffers `ops.gmw_pack_records` fills and
+                    `refine_packed` reads, with the checks both users need;
   RecordRefiner     the same refinement fed from a detector's decode on the device: `ops.gmw_pack_records` gathers the kept
                     candidates of each image batch into `batch_size` accumulation buffers (`plan_packs` splits a call at the
                     capacity), a full buffer is refined and its result copied to a pinned slot behind an event;
@@ -140,6 +142,35 @@ def plan_packs(n_new, filled, cap):
     return pieces
 
 
+class PackBuffers:
+    """`cap` records in the extractors' layout on `device`: the seven buffers `ops.gmw_pack_records` writes and `refine_packed`
+    reads, and the model's pair tables as the kernel takes them.  `who` names the caller in the refusals, which come before
+    anything is allocated."""
+
+    def __init__(self, model, device, cap, nk, who):
+        if nk != NUM_KPTS or int(model.num_kpts) != NUM_KPTS:
+            raise ValueError("%s: %d key points (model: %d); GMW's pair tables are for %d" % (who, nk, int(model.num_kpts), NUM_KPTS))
+        if cap < 1:
+            raise ValueError("%s: %d records per refinement call" % (who, cap))
+        if next(model.parameters()).dtype != torch.float32:
+            raise ValueError("%s runs in float32 (the model is %s)" % (who, next(model.parameters()).dtype))
+        self.model, self.cap = model, int(cap)
+        P = nk * (nk - 1) // 2
+        self.pair_i = model.pair_i.to(device=device, dtype=torch.int32).contiguous()
+        self.pair_j = model.pair_j.to(device=device, dtype=torch.int32).contiguous()
+        shapes = ((4, P), (6, P), (nk, 2), (nk, 3), (1,), (3,), (3,))        # e4, e6, k2, k3, rot, loc, dim
+        self.buffers = [torch.zeros((self.cap,) + s, dtype=torch.float32, device=device) for s in shapes]
+
+    def pack(self, rows, k2, k3, src, dst0):
+        """Records `src` (int32 row numbers on the device) of a decoded batch into the buffers from row `dst0` on: one launch."""
+        from dcd_amd import ops
+        ops.gmw_pack_records(rows, k2, k3, src, dst0, self.pair_i, self.pair_j, *self.buffers)
+
+    def refine(self, count):
+        """`refine_packed` of the first `count` records: (pred_depth (count), pred_location (count, 3)) on the device."""
+        return refine_packed(self.model, *(b[:count] for b in self.buffers))
+
+
 class RecordRefiner:
     """GMW's refinement fed by a detector's batched decode, without leaving the device: `add` gathers the named candidates of a
     decoded image batch into `batch_size` accumulation buffers in the extractors' layout (one `ops.gmw_pack_records` launch per
@@ -152,19 +183,9 @@ class RecordRefiner:
     Everything is enqueued on the stream current at the call."""
 
     def __init__(self, model, device, batch_size=256, nk=NUM_KPTS):
-        if nk != NUM_KPTS or int(model.num_kpts) != NUM_KPTS:
-            raise ValueError("RecordRefiner: %d key points (model: %d); GMW's pair tables are for %d"
-                             % (nk, int(model.num_kpts), NUM_KPTS))
-        if batch_size < 1:
-            raise ValueError("batch size %d" % batch_size)
-        if next(model.parameters()).dtype != torch.float32:
-            raise ValueError("RecordRefiner runs in float32 (the model is %s)" % next(model.parameters()).dtype)
-        self.model, self.device, self.cap, self.nk = model, torch.device(device), int(batch_size), nk
-        P = nk * (nk - 1) // 2
-        self.pair_i = model.pair_i.to(device=self.device, dtype=torch.int32).contiguous()
-        self.pair_j = model.pair_j.to(device=self.device, dtype=torch.int32).contiguous()
-        shapes = ((4, P), (6, P), (nk, 2), (nk, 3), (1,), (3,), (3,))        # e4, e6, k2, k3, rot, loc, dim
-        self.buffers = [torch.zeros((self.cap,) + s, dtype=torch.float32, device=self.device) for s in shapes]
+        self.model, self.device, self.nk = model, torch.device(device), nk
+        self.packs = PackBuffers(model, self.device, batch_size, nk, "RecordRefiner")
+        self.cap = self.packs.cap
         self.filled = 0
         self.flushes = 0
         self._out = [torch.empty((self.cap, 4), dtype=torch.float32).pin_memory() for _ in range(2)]      # z | location
@@ -201,7 +222,7 @@ class RecordRefiner:
 
     def _flush(self):
         count, slot = self.filled, self.flushes % 2
-        z, ploc = refine_packed(self.model, *(b[:count] for b in self.buffers))
+        z, ploc = self.packs.refine(count)
         self._collect()                                        # the flush before this one: its slot is the other one
         self._out[slot][:count].copy_(torch.cat((z.unsqueeze(1), ploc), dim=1), non_blocking=True)
         self._out_events[slot].record()
@@ -212,7 +233,6 @@ class RecordRefiner:
     def add(self, rows, k2, k3, src_host):
         """rows (n_rows, 14), k2 (n_rows, nk, 2), k3 (n_rows, nk, 3): a decoded batch on the device; src_host: the row numbers to
         keep, in order (a sequence of ints on the host)."""
-        from dcd_amd import ops
         src_host = np.asarray(src_host, dtype=np.int32).reshape(-1)
         if k2.shape[1] != self.nk:
             raise ValueError("RecordRefiner.add: %d key points per record, %d expected" % (k2.shape[1], self.nk))
@@ -220,7 +240,7 @@ class RecordRefiner:
             return
         src = self._upload(src_host)
         for start, count, flush in plan_packs(len(src_host), self.filled, self.cap):
-            ops.gmw_pack_records(rows, k2, k3, src[start:start + count], self.filled, self.pair_i, self.pair_j, *self.buffers)
+            self.packs.pack(rows, k2, k3, src[start:start + count], self.filled)
             self.filled += count
             if flush:
                 self._flush()

@@ -33,6 +33,7 @@ import time
 
 import torch
 
+from dcd_amd.engine.passes import load_gmw_state
 from dcd_amd.engine.trainer import ClipAdamW, _host_state_value, guard_nonfinite_step
 from .data import ResidentRecords, epoch_order, load_train_data
 from .step import gmw_losses, gmw_train_step
@@ -218,7 +219,7 @@ def train_gmw(model, records, log_dir, epochs=100, batch_size=16, lr=1e-4, weigh
     if resume:
         checkpoint = torch.load(resume, map_location="cpu", weights_only=False)
         start_epoch, best_mAP = int(checkpoint["epoch"]), checkpoint["best_mAP"]
-        model.load_state_dict({k.replace("module.", ""): v for k, v in checkpoint["state_dict"].items()})
+        load_gmw_state(model, checkpoint["state_dict"])
         load_optimizer_state(optimizer, checkpoint["optimizer"])
         scheduler.load_state_dict(checkpoint["scheduler"])
         print("=> loaded checkpoint '{}' (epoch {})".format(resume, checkpoint["epoch"]))
@@ -305,25 +306,16 @@ def records_from_detector(ckpt, root, split="train", batch=8, opts=(), device="c
     """The collection pass of a trained detector over a KITTI split (`engine.train.collect_gmw_records`): loads the checkpoint, walks
     the split's labelled images in file order without flips, in whole batches, releases the detector and returns the
     `ResidentRecords`."""
-    import ast
     from dcd_amd.config import get_cfg
     from dcd_amd.data.batches import ResidentBatches
     from dcd_amd.data.kitti_files import KittiFiles
     from dcd_amd.data.resident import ResidentSplit
-    from dcd_amd.engine.train import collect_gmw_records, resume
-    from dcd_amd.model.detector import KeypointDetector
-    parsed = []
-    for k, v in zip(list(opts)[0::2], list(opts)[1::2]):
-        try:
-            v = ast.literal_eval(v) if isinstance(v, str) else v
-        except (ValueError, SyntaxError):
-            pass
-        parsed += [k, v]
-    cfg = get_cfg(opts=["MODEL.PRETRAIN", False, "TEST.GENERATE_GMW", True] + parsed)
+    from dcd_amd.engine.passes import load_detector, parse_overrides
+    from dcd_amd.engine.train import collect_gmw_records
+    cfg = get_cfg(opts=["MODEL.PRETRAIN", False, "TEST.GENERATE_GMW", True] + parse_overrides(opts))
     device = torch.device(device)
     files = KittiFiles(root, split, cfg, is_train=True)
-    model = KeypointDetector(cfg).to(device)
-    resume(ckpt, model)
+    model, _ = load_detector(cfg, ckpt, device)
     batch = max(1, min(int(batch), len(files)))
     source = ResidentBatches(ResidentSplit(files, cfg, device), batch, seed=0, is_train=False)
     iterations = len(files) // batch                            # whole batches, as the reference's pass (trainer.py:97-98)

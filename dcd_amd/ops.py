@@ -14,6 +14,7 @@ import os
 import torch
 
 from . import _lib
+from .structures.params_3d import _typed
 
 
 def _f32c(t):
@@ -232,14 +233,6 @@ _ROWS_TARGETS = (("reg_mask", torch.uint8), ("trunc_mask", torch.uint8), ("find_
                  ("Calib_P", torch.float32), ("calib", torch.float32))
 _ROWS_FIELD = {"target_centers": "centers", "keypoints_depth_mask": "kp_depth_mask", "extra_kpts_2d": "kpts2d",
                "extra_kpts_3d": "kpts3d", "Calib_P": "calib_P"}
-
-
-def _typed(t, dtype):
-    if t.dtype == torch.bool and dtype == torch.uint8:
-        t = t.view(torch.uint8)
-    elif t.dtype != dtype:
-        t = t.to(dtype)
-    return t.contiguous()
 
 
 class _LossRows(torch.autograd.Function):

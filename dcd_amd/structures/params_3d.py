@@ -61,6 +61,15 @@ def stack_field(targets, name):
     return torch.stack(ts)
 
 
+def _typed(t, dtype):
+    """A target field as the dtype a kernel reads, contiguous; a bool mask becomes bytes without a copy."""
+    if t.dtype == torch.bool and dtype == torch.uint8:
+        t = t.view(torch.uint8)
+    elif t.dtype != dtype:
+        t = t.to(dtype)
+    return t.contiguous()
+
+
 def collate_fields(targets):
     """Re-home every tensor field of a list of ParamsList in one batched tensor per field (what a collate function of the data
     loader does once per batch); the per-image fields become views, so later stacking is free (`stack_field`)."""

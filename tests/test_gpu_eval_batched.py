@@ -1,6 +1,7 @@
 """The batched evaluation (`engine.inference.inference(batch_size > 1 | gen_out_dir=...)`) on the four-image fixture directory:
 against the one-image loop file by file, the records of the same pass against `generate_infer_data`, one model call per
-validation image from `do_train`, no host synchronisation inside the loop, and the command line."""
+validation image from `do_train`, no host synchronisation inside the loop, the walker under both passes (`eval_batches`), and the
+command line."""
 import json
 import os
 import subprocess
@@ -158,6 +159,63 @@ def test_the_loop_never_waits_on_an_image(world, tmp_path, monkeypatch):
     assert counts == {"item": 0, "cpu": 0, "nonzero": 0, "synchronize": 0, "event": 2, "other event": 0}, counts
     assert uploads <= 2
     assert list(records) == world["ids"] and sorted(os.listdir(folder)) == [i + ".txt" for i in world["ids"]]
+
+
+def _same_batch(got, want):
+    """Two batches of the input pipeline, bit for bit: the images and every tensor or string field of every target."""
+    def bits(t):
+        return t.contiguous().reshape(-1).view(torch.uint8)
+    (images, targets), (ref_images, ref_targets) = got, want
+    assert images.dtype == ref_images.dtype and images.shape == ref_images.shape and torch.equal(bits(images), bits(ref_images))
+    assert len(targets) == len(ref_targets)
+    compared = 0
+    for t, r in zip(targets, ref_targets):
+        assert t.fields() == r.fields() and tuple(t.size) == tuple(r.size)
+        for name in t.fields():
+            a, b = t.get_field(name), r.get_field(name)
+            assert type(a) is type(b), name
+            if torch.is_tensor(a):
+                assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b)), name
+                compared += 1
+            elif isinstance(a, str):
+                assert a == b, name
+    assert compared >= len(targets)                                    # (the targets do carry tensors)
+
+
+def test_eval_batches_walks_the_split_and_stops_its_threads(world):
+    """`eval_batches` at batch size 3 over the four images: batches [0, 1, 2] and [3], bit-equal to `EvalBatches.get(k)`; and a
+    loop body that raises leaves no thread pool behind: the executor refuses further work by the time the exception is out."""
+    from dcd_amd.data.batches import EvalBatches, eval_batches
+    plain = EvalBatches(world["files"], world["pipe"], 3, 2)
+    try:
+        want = [plain.get(k) for k in range(plain.num_batches)]
+    finally:
+        plain.close()
+    torch.cuda.synchronize()
+    assert len(want) == 2
+    seen = []
+    with eval_batches(world["files"], world["pipe"], 3, 2) as walk:
+        for k, indices, images, targets in walk:
+            seen.append((k, indices))
+            torch.cuda.synchronize()
+            _same_batch((images, targets), want[k])
+        pool = walk.source._pool
+        pool.submit(int).result()                                      # still open inside the block
+    assert seen == [(0, [0, 1, 2]), (1, [3])]
+    with pytest.raises(RuntimeError, match="shutdown"):
+        pool.submit(int)
+
+    class Stop(Exception):
+        pass
+    pools = []
+    with pytest.raises(Stop):
+        with eval_batches(world["files"], world["pipe"], 3, 2) as walk:
+            for k, indices, images, targets in walk:
+                pools.append(walk.source._pool)
+                raise Stop()
+    assert len(pools) == 1 and pools[0]._shutdown
+    with pytest.raises(RuntimeError, match="shutdown"):
+        pools[0].submit(int)
 
 
 def test_command_line_evaluates_a_checkpoint(world, tmp_path):

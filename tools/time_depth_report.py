@@ -24,29 +24,10 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from tools.kernel_trace import traced_child
 from tools.time_detector_eval import KITTI_SIZES, write_split
 
 ONCE_CALLS = 20
-
-
-def traced(work):
-    """{kernel name: (calls, total us)} of a child process running this file with `--once loop`."""
-    import csv
-    import glob
-    import subprocess
-    tdir = os.path.join(work, "trace_loop")
-    os.makedirs(tdir)
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tdir, "-o", "loop", "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--once", "loop"]
-    r = subprocess.run(cmd, cwd=tdir, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    if r.returncode != 0:
-        raise RuntimeError("rocprofv3 run failed (%d):\n%s" % (r.returncode, r.stdout[-2000:]))
-    found = {}
-    for path in glob.glob(os.path.join(tdir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(path)):
-            calls, total = found.get(row["Name"], (0, 0.0))
-            found[row["Name"]] = (calls + int(row["Calls"]), total + float(row["TotalDurationNs"]) / 1e3)
-    return found
 
 
 def main():
@@ -128,7 +109,7 @@ def main():
                      % (med["depth report with gmw="] - med["depth report"],
                         1e3 * (med["depth report with gmw="] - med["depth report"]) / slots))
         if not args.no_trace:
-            found = traced(work)
+            found = traced_child(__file__, "loop", work, 600)
             lines.append("one batch of 8 x %d slots (rocprofv3 --kernel-trace --stats, a child of its own, %d calls):"
                          % (cfg.DATASETS.MAX_OBJECTS, ONCE_CALLS))
             for kernel in ("depth_estimates", "depth_accumulate"):

@@ -15,12 +15,9 @@ route beyond the spread of (a) at any batch size; the file says whether that hol
 
     python tools/time_detector_eval.py [--frames 192] [--reps 3] [--no-trace] [--out profiles/detector_eval.txt]"""
 import argparse
-import csv
-import glob
 import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 import time
@@ -29,6 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
+
+from tools.kernel_trace import traced_child
 
 KITTI_SIZES = ((1242, 375), (1224, 370), (1238, 374), (1280, 384))        # (w, h)
 ONCE_CALLS = 20
@@ -54,23 +53,6 @@ def write_split(root, n):
         f.write("".join("%06d\n" % i for i in range(n)))
     with open(os.path.join(root, "kpts_ann", "kpts_ann_train.json"), "w") as f:
         json.dump(out_ann, f)
-
-
-def traced(work, mode):
-    """{kernel name: (calls, total us)} of a child process running `--once MODE`."""
-    tdir = os.path.join(work, "trace_" + mode)
-    os.makedirs(tdir)
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tdir, "-o", mode, "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--once", mode]
-    r = subprocess.run(cmd, cwd=tdir, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    if r.returncode != 0:
-        raise RuntimeError("rocprofv3 run failed (%d):\n%s" % (r.returncode, r.stdout[-2000:]))
-    found = {}
-    for path in glob.glob(os.path.join(tdir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(path)):
-            calls, total = found.get(row["Name"], (0, 0.0))
-            found[row["Name"]] = (calls + int(row["Calls"]), total + float(row["TotalDurationNs"]) / 1e3)
-    return found
 
 
 def main():
@@ -166,7 +148,7 @@ def main():
                                                        decode_us["chain"] / decode_us["fused"]))
         # (c) kernel trace, children of their own
         if not args.no_trace:
-            found = {mode: traced(work, mode) for mode in ("predictor", "fused", "chain")}
+            found = {mode: traced_child(__file__, mode, work, 600) for mode in ("predictor", "fused", "chain")}
             base_calls = sum(c for c, _ in found["predictor"].values())
             for mode in ("fused", "chain"):
                 calls = sum(c for c, _ in found[mode].values())

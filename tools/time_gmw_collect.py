@@ -13,11 +13,8 @@ Writes the figures to --out (default profiles/gmw_collect.txt).  No ratio is ask
 
     python tools/time_gmw_collect.py [--frames 64] [--reps 3] [--no-trace] [--out profiles/gmw_collect.txt]"""
 import argparse
-import csv
-import glob
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 import time
@@ -29,26 +26,10 @@ import numpy as np
 import torch
 
 from time_detector_eval import KITTI_SIZES, write_split
+from tools.kernel_trace import traced_child
 
 ONCE_CALLS = 20
 BATCH = 8
-
-
-def traced(work, mode):
-    """{kernel name: (calls, total us)} of a child process running `--once MODE`."""
-    tdir = os.path.join(work, "trace_" + mode)
-    os.makedirs(tdir)
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tdir, "-o", mode, "--output-format", "csv", "--",
-           sys.executable, os.path.abspath(__file__), "--once", mode]
-    r = subprocess.run(cmd, cwd=tdir, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("rocprofv3 run failed (%d):\n%s" % (r.returncode, r.stdout[-2000:]))
-    found = {}
-    for path in glob.glob(os.path.join(tdir, "**", "*kernel_stats.csv"), recursive=True):
-        for row in csv.DictReader(open(path)):
-            calls, total = found.get(row["Name"], (0, 0.0))
-            found[row["Name"]] = (calls + int(row["Calls"]), total + float(row["TotalDurationNs"]) / 1e3)
-    return found
 
 
 def once(mode, dev):
@@ -145,7 +126,7 @@ def main():
         lines.append("  run-to-run spread of the file route (its two series): %.1f %%; the device route against it: %.2fx -- %s"
                      % (100 * spread, ratio, verdict))
         if not args.no_trace:
-            found = {mode: traced(work, mode) for mode in ("base", "collect")}
+            found = {mode: traced_child(__file__, mode, work, 300) for mode in ("base", "collect")}
             calls = {m: sum(c for c, _ in f.values()) for m, f in found.items()}
             us = {m: sum(t for _, t in f.values()) for m, f in found.items()}
             lines.append("TrainRecordCollector.add on a batch of %d (rocprofv3 --kernel-trace --stats, children of their own, %d calls): "
