@@ -3,9 +3,27 @@
 Module names / shapes equal the reference's so state dicts are interchangeable:
 `class_head` (3x3 conv, BN, ReLU, 1x1 conv), `reg_features[i]` (3x3 conv, BN, ReLU), `reg_heads[i][j]` (1x1 conv),
 `trunc_heatmap_conv`, `trunc_offset_conv` (Conv1d k3 replicate-pad, BN1d, [ReLU], Conv1d k1).
-Differences in execution only: the per-image Python scatter loop of the edge fusion (:193-196, one host sync per
-image) is a single masked `index_put_(accumulate=True)`.
+
+`forward` is the reference's dense form (`reg` (B, 415, H, W); the per-image Python scatter loop of the edge fusion, :193-196, one
+host sync per image, is a single masked `index_put_(accumulate=True)`) or one of two sparse forms, training (`sparse_training_heads`)
+and evaluation (`sparse_eval_heads`, `heads_at`): the regression heads at listed cells only (`reg_pois` (B, M, 415), `reg` None),
+composed of five steps, each decision taken in one of them:
+  1 `_edge_cells`    the border cells of the edge fusion from the targets, once per forward (None: fusion off)
+  2 `_trunk_inputs`  deeper head: the two stems, the regression stem fanned out; moments route: the feature map itself (two consumers);
+                     else `ops.fan_out` over the class trunk and every regression trunk (device tensor that needs a gradient) or the tensor
+  3 `_class_branch`  trunk, 1x1 output layer (training, float32 device map, edge fusion: one node with the gather at the edge cells,
+                     `ops.head_out_and_gather`), the class map's edge term, sigmoid
+  4 `_trunks_at`     the trunks at the cells, by `_sparse_route`, first match:
+       frozen   not deeper head, `_HEAD_ROWS`, float32 device tensor, no gradients, `head_rows_ok`, `trunk_moments.frozen` -> `trunks_at_frozen`
+       moments  not deeper head, `trunk_moments.usable` -> `trunk_moments.trunks_at`, stacked
+       each     per trunk `BatchNorm2d.forward_at` where the norm has it and holds the activation; else (GN, leaky ReLU) dense + POI gather
+  5 `_heads`         `ops.head_rows` on the frozen route and on the moments route with `_HEAD_ROWS`, a float32 device tensor and
+                     `head_rows_ok`, else one `F.linear` per head (also on the device); the edge term of `3d_offset` is added here
+`heads_at` and the second half of the sparse evaluation are steps 4 (frozen) and 5 behind `_sparse_eval_refusal`.
 """
+import os
+from typing import NamedTuple
+
 import numpy as np
 import torch
 from torch import nn
@@ -14,16 +32,12 @@ from torch.nn import functional as F
 from dcd_amd.structures.params_3d import stack_field
 from dcd_amd import ops
 from dcd_amd.model import registry
-from dcd_amd.model.layers.utils import select_point_of_interest, sigmoid_hm
+from dcd_amd.model.layers.utils import select_point_of_interest, select_topk, sigmoid_hm
 from dcd_amd.model.make_layers import group_norm, _fill_fc_weights
 from dcd_amd.model.backbone.DCNv2.dcn_v2 import DCN
 from dcd_amd.model.layers.norm import BatchNorm2d
 from dcd_amd.model.layers.conv import Conv2d
 from dcd_amd.model.head import trunk_moments
-
-import os
-
-_EDGE_FAST = os.environ.get("DCD_EDGE_BRANCH_GEMM", "1") != "0"      # 0: the edge-fusion branches on the stock Conv1d / BatchNorm1d (A/B timing)
 
 
 class EdgeBranch(nn.Sequential):
@@ -35,7 +49,7 @@ class EdgeBranch(nn.Sequential):
 
     def forward(self, x):
         conv1, bn, act, conv2 = self[0], self[1], self[2], self[3]
-        if not (_EDGE_FAST and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and isinstance(conv1, nn.Conv1d)
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and isinstance(conv1, nn.Conv1d)
                 and conv1.kernel_size == (3,) and conv1.stride == (1,) and conv1.dilation == (1,) and conv1.groups == 1
                 and conv1.padding_mode == "replicate" and conv1.padding == (1,) and conv1.bias is not None):
             return super().forward(x)
@@ -54,8 +68,17 @@ class EdgeBranch(nn.Sequential):
             w2 = conv2.weight.squeeze(-1)
             return torch.baddbmm(conv2.bias.view(1, -1, 1), w2.unsqueeze(0).expand(y.shape[0], -1, -1), y)
         return conv2(y)
-_HEAD_FUSED = os.environ.get("DCD_HEAD_FUSED", "1") != "0"      # 0: stock 1x1 conv + separate gather (A/B timing)
+
+
 _HEAD_ROWS = os.environ.get("DCD_HEAD_ROWS", "1") != "0"        # 0: one F.linear per regression head (A/B timing, CPU tests)
+
+
+class EdgeCells(NamedTuple):
+    """The border cells of the edge fusion, from the targets: K cells per image, the first `edge_len` of them real."""
+    xi: torch.Tensor        # (B, K) int64 column
+    yi: torch.Tensor        # (B, K) int64 row
+    lin: torch.Tensor       # (B, K) int64 linear cell index yi * W + xi
+    valid: torch.Tensor     # (B, K) bool
 
 
 @registry.PREDICTOR.register("Base_Predictor")
@@ -105,6 +128,8 @@ class _predictor(nn.Module):
             self.reg_head_pre = self._deep_stem()
         self.reg_features = nn.ModuleList()
         self.reg_heads = nn.ModuleList()
+        self.head_trunk = []            # trunk index of every head, in output-channel order
+        channels = 0
         for idx, keys in enumerate(self.regression_head_cfg):
             self.reg_features.append(nn.Sequential(
                 Conv2d(trunk_in, self.head_conv, kernel_size=3, padding=1, bias=False),
@@ -117,9 +142,15 @@ class _predictor(nn.Module):
                     torch.nn.init.xavier_normal_(out_head.weight, gain=0.01)
                 if key == '3d_offset':   # the edge fusion is applied to this branch
                     self.offset_index = [idx, key_index]
+                    self.offset_channel = channels          # first output channel of the 3d_offset head
                 _fill_fc_weights(out_head, 0)
                 heads.append(out_head)
+                self.head_trunk.append(idx)
+                channels += out_head.out_channels
             self.reg_heads.append(heads)
+        # the shapes ops.head_rows takes: 1x1 output layers (built above) over a trunk of at most 256 channels, at most 16 heads
+        self.head_rows_ok = (len(self.head_trunk) <= 16 and len(self.reg_features) <= 16 and self.head_conv <= 256
+                             and self.head_conv % 4 == 0 and channels <= 1024)
 
         # --- edge (truncation) feature fusion
         self.enable_edge_fusion = cfg.MODEL.HEAD.ENABLE_EDGE_FUSION
@@ -166,19 +197,22 @@ class _predictor(nn.Module):
             DCN(self.head_conv, self.head_conv, kernel_size=(3, 3), stride=1, padding=1, dilation=1, deformable_groups=1),
             self.norm_func(self.head_conv), self._get_active_func())
 
-    def _edge_fusion(self, feature_cls, reg_feature, output_cls, output_reg, targets):
+    def _edge_cells(self, targets, w):
+        """The border cells on a map `w` cells wide (None when the edge fusion is off): no device->host sync."""
+        if not self.enable_edge_fusion:
+            return None
+        edge_indices = stack_field(targets, "edge_indices")          # B x K x 2 (x, y)
+        edge_lens = stack_field(targets, "edge_len").view(-1, 1)      # B x 1
+        xi, yi = edge_indices[:, :, 0].long(), edge_indices[:, :, 1].long()
+        valid = torch.arange(edge_indices.shape[1], device=edge_indices.device).view(1, -1) < edge_lens
+        return EdgeCells(xi, yi, yi * w + xi, valid)
+
+    def _edge_fusion(self, feature_cls, reg_feature, output_cls, output_reg, targets, cells):
         """Sample both feature maps along the image border, run the two Conv1d branches and add the result back
         at the border cells (detector_predictor.py:172-196)."""
-        b = feature_cls.shape[0]
-        edge_indices = stack_field(targets, "edge_indices")          # B x K x 2 (x, y)
-        edge_lens = stack_field(targets, "edge_len").view(b, 1)       # B x 1
-        out_w = stack_field(targets, "final_output_w").float().view(-1, 1, 1)
-        out_h = stack_field(targets, "final_output_h").float().view(-1, 1, 1)
-
-        K = edge_indices.shape[1]
-        bi = torch.arange(b, device=edge_indices.device).view(b, 1, 1)
-        yi = edge_indices[:, :, 1].long().view(b, 1, K)
-        xi = edge_indices[:, :, 0].long().view(b, 1, K)
+        b, K = cells.lin.shape
+        bi = torch.arange(b, device=cells.lin.device).view(b, 1, 1)
+        yi, xi = cells.yi.view(b, 1, K), cells.xi.view(b, 1, K)
         # final_output_w/h are the configured output size for every sample (kitti.py sets them from the same cfg keys);
         # compared as Python ints so that no device->host sync is needed here
         if self.exact_edge_gather and self.output_width == feature_cls.shape[3] and self.output_height == feature_cls.shape[2]:
@@ -190,157 +224,140 @@ class _predictor(nn.Module):
             edge_cls_feature = feature_cls[bi, ci, yi, xi]
             edge_offset_feature = reg_feature[bi, ci, yi, xi]
         else:
-            grid = edge_indices.view(b, -1, 1, 2).float()
-            grid = torch.stack((grid[..., 0] / (out_w - 1) * 2 - 1, grid[..., 1] / (out_h - 1) * 2 - 1), dim=-1)
+            out_w = stack_field(targets, "final_output_w").float().view(-1, 1, 1)
+            out_h = stack_field(targets, "final_output_h").float().view(-1, 1, 1)
+            gx, gy = cells.xi.view(b, K, 1).float(), cells.yi.view(b, K, 1).float()
+            grid = torch.stack((gx / (out_w - 1) * 2 - 1, gy / (out_h - 1) * 2 - 1), dim=-1)
             fused = torch.cat((feature_cls, reg_feature), dim=1)
             edge_features = F.grid_sample(fused, grid.type_as(fused), align_corners=True).squeeze(-1)
             edge_cls_feature = edge_features[:, :self.head_conv, ...]
             edge_offset_feature = edge_features[:, self.head_conv:, ...]
         edge_cls_output = self.trunc_heatmap_conv(edge_cls_feature)
         edge_offset_output = self.trunc_offset_conv(edge_offset_feature)
-        valid = (torch.arange(K, device=edge_indices.device).view(1, K) < edge_lens).to(edge_cls_output.dtype)
+        valid = cells.valid.to(edge_cls_output.dtype)
         for out, vals in ((output_cls, edge_cls_output), (output_reg, edge_offset_output)):
             ci = torch.arange(out.shape[1], device=out.device).view(1, -1, 1)
             out.index_put_((bi, ci, yi, xi), vals * valid.unsqueeze(1), accumulate=True)
 
-    def _edge_fusion_at_pois(self, edge_feature, edge_lin, valid, centers_lin):
+    def _edge_fusion_cls(self, feature_cls, output_cls, cells, gathered=None):
+        """The class-map half of `_edge_fusion` (dense: the focal loss reads every cell).  gathered: feature_cls at the border
+        cells (B, K, C) when the caller already has it (ops.head_out_and_gather)."""
+        b, K = cells.lin.shape
+        if feature_cls.is_cuda and output_cls.dtype == torch.float32 and output_cls.is_contiguous():
+            # gather / scatter-add at linear cell indices on the HIP kernels (one launch each)
+            at_edges = gathered if gathered is not None else ops.select_point_of_interest(b, cells.lin, feature_cls)
+            edge_cls_output = self.trunc_heatmap_conv(at_edges.transpose(1, 2))
+            vals = (edge_cls_output * cells.valid.unsqueeze(1).to(edge_cls_output.dtype)).transpose(1, 2)
+            return ops.scatter_add_at(output_cls, vals, cells.lin)
+        bi = torch.arange(b, device=cells.lin.device).view(b, 1, 1)
+        yi, xi = cells.yi.view(b, 1, K), cells.xi.view(b, 1, K)
+        ci = torch.arange(self.head_conv, device=feature_cls.device).view(1, -1, 1)
+        edge_cls_output = self.trunc_heatmap_conv(feature_cls[bi, ci, yi, xi])
+        co = torch.arange(output_cls.shape[1], device=output_cls.device).view(1, -1, 1)
+        output_cls.index_put_((bi, co, yi, xi), edge_cls_output * cells.valid.unsqueeze(1).to(edge_cls_output.dtype), accumulate=True)
+        return output_cls
+
+    def _edge_fusion_at_pois(self, edge_feature, cells, centers_lin):
         """Edge-fusion term of the 3d_offset head at the object centres: what `_edge_fusion` would have accumulated into the
         dense map at those cells (detector_predictor.py:172-196, duplicates of a border cell included).
         edge_feature (B, 256, K): trunk output at the border cells."""
         edge_offset_output = self.trunc_offset_conv(edge_feature)                            # B x 2 x K
-        hit = (centers_lin.unsqueeze(2) == edge_lin.unsqueeze(1)) & valid.unsqueeze(1)       # B x M x K
+        hit = (centers_lin.unsqueeze(2) == cells.lin.unsqueeze(1)) & cells.valid.unsqueeze(1)  # B x M x K
         return torch.bmm(hit.to(edge_offset_output.dtype), edge_offset_output.transpose(1, 2))  # B x M x 2
 
-    def _forward_sparse(self, features, targets):
-        """Training forward with the regression heads evaluated at the object centres only.  The trunks' BN + ReLU is
-        evaluated at those positions too (`BatchNorm2d.forward_at`): its dense output map is never written, and its backward
-        needs one read of the conv output and one write of the gradient instead of seven tensor passes."""
-        # one feature map feeds all twelve trunks: its gradient is summed by one kernel instead of eleven pairwise additions
+    def _sparse_route(self, features):
+        """(how the trunks are evaluated at positions: "frozen" | "moments" | "each", whether the heads run on ops.head_rows)."""
+        if not self.deeper_head:
+            rows = _HEAD_ROWS and features.is_cuda and features.dtype == torch.float32 and self.head_rows_ok
+            if rows and not torch.is_grad_enabled() and trunk_moments.frozen(self.reg_features, features):
+                return "frozen", True      # --generate_for_GMW pass: BatchNorm frozen, no gradients -> no statistics, no dense trunk output
+            if all(isinstance(t[2], nn.Identity) for t in self.reg_features) and trunk_moments.usable(self.reg_features, features):
+                return "moments", rows     # all trunks at once from the Gram matrix of the shared input's 3x3 patches (trunk_moments.py)
+        return "each", False
+
+    def _trunk_inputs(self, features, route):
+        """(input of the class trunk, input of every regression trunk).  One feature map feeds all twelve trunks: fanned out, its
+        gradient is summed by one kernel instead of eleven pairwise additions."""
         n_reg = len(self.reg_features)
         if self.deeper_head:
-            feat_cls_in = self.cls_head_pre(features)
-            feat_reg_in = self.reg_head_pre(features)
-            reg_inputs = ops.fan_out(feat_reg_in, n_reg) if feat_reg_in.is_cuda and feat_reg_in.requires_grad else [feat_reg_in] * n_reg
-        elif trunk_moments.ENABLED and trunk_moments.usable(self.reg_features, features):
-            feat_cls_in, reg_inputs = features, [features] * n_reg          # two consumers only: the class trunk and the moments
-        elif features.is_cuda and features.requires_grad:
+            feat_cls_in, feat_reg_in = self.cls_head_pre(features), self.reg_head_pre(features)
+            fan = feat_reg_in.is_cuda and feat_reg_in.requires_grad
+            return feat_cls_in, ops.fan_out(feat_reg_in, n_reg) if fan else [feat_reg_in] * n_reg
+        if route != "moments" and features.is_cuda and features.requires_grad:
             fans = ops.fan_out(features, n_reg + 1)
-            feat_cls_in, reg_inputs = fans[0], fans[1:]
-        else:
-            feat_cls_in, reg_inputs = features, [features] * n_reg
+            return fans[0], fans[1:]
+        return features, [features] * n_reg         # moments: two consumers only, the class trunk and the moments
+
+    def _class_branch(self, feat_cls_in, cells, gather_node):
+        """The dense class map with its edge term, after the sigmoid; gather_node: output layer and edge gather as one node (training)."""
         feature_cls = self.class_head[:-1](feat_cls_in)
-        b, _, h, w = feature_cls.shape
         last = self.class_head[-1]
-        edge_cls_feature = None
-        if (_HEAD_FUSED and self.enable_edge_fusion and feature_cls.is_cuda and feature_cls.dtype == torch.float32 and isinstance(last, nn.Conv2d)
+        at_edges = None
+        if (gather_node and cells is not None and feature_cls.is_cuda and feature_cls.dtype == torch.float32 and isinstance(last, nn.Conv2d)
                 and last.kernel_size == (1, 1) and last.stride == (1, 1) and last.padding == (0, 0) and last.groups == 1):
             # the class head's output layer and the edge-fusion gather read the same feature map: one node, one gradient write
-            ei = stack_field(targets, "edge_indices")
-            output_cls, edge_cls_feature = ops.head_out_and_gather(feature_cls, last.weight, last.bias,
-                                                                   ei[:, :, 1].long() * w + ei[:, :, 0].long())
+            output_cls, at_edges = ops.head_out_and_gather(feature_cls, last.weight, last.bias, cells.lin)
         else:
             output_cls = last(feature_cls)
-        centers = stack_field(targets, "target_centers")              # B x M x 2 (x, y)
-        centers_lin = centers[:, :, 1].long() * w + centers[:, :, 0].long()                  # B x M
-        M = centers_lin.shape[1]
-        if self.enable_edge_fusion:
-            edge_indices = stack_field(targets, "edge_indices")      # B x K x 2 (x, y)
-            edge_lens = stack_field(targets, "edge_len").view(b, 1)
-            K = edge_indices.shape[1]
-            edge_lin = edge_indices[:, :, 1].long() * w + edge_indices[:, :, 0].long()       # B x K
-            edge_valid = torch.arange(K, device=edge_lin.device).view(1, K) < edge_lens      # B x K
-        outs = []
-        # All trunks at once from the Gram matrix of the shared input's 3x3 patches: no dense trunk output exists (trunk_moments.py)
-        moments = None
-        frozen_bn = (not self.deeper_head and _HEAD_ROWS and features.is_cuda and features.dtype == torch.float32
-                     and not torch.is_grad_enabled() and self._head_rows_ok() and trunk_moments.frozen(self.reg_features, reg_inputs[0]))
-        if frozen_bn or (not self.deeper_head and all(isinstance(fl[2], nn.Identity) for fl in self.reg_features)
-                         and trunk_moments.usable(self.reg_features, reg_inputs[0])):
-            extra = (self.offset_index[0], edge_lin) if self.enable_edge_fusion else None
-            if frozen_bn or (_HEAD_ROWS and features.is_cuda and features.dtype == torch.float32 and self._head_rows_ok()):
-                # every 1x1 output layer at the object centres in ONE launch (ops.head_rows) instead of a GEMM per head, their
-                # concatenation and -- backward -- two GEMMs, a bias sum and a slice copy per head
-                if frozen_bn:      # --generate_for_GMW pass: BatchNorm frozen, no gradients -> no statistics, no dense trunk output
-                    at_centres, at_extra = trunk_moments.trunks_at_frozen(reg_inputs[0], self.reg_features, centers_lin, extra)
-                else:
-                    at_centres, at_extra = trunk_moments.trunks_at(reg_inputs[0], self.reg_features, centers_lin, extra, stacked=True)
-                heads = [(i, h) for i, hs in enumerate(self.reg_heads) for h in hs]
-                reg_pois = ops.head_rows(at_centres.reshape(n_reg, b * M, self.head_conv), [i for i, _ in heads],
-                                         [h.weight for _, h in heads], [h.bias for _, h in heads]).view(b, M, -1)
-                if self.enable_edge_fusion:
-                    first = sum(len(hs) for hs in self.reg_heads[:self.offset_index[0]]) + self.offset_index[1]
-                    ch0 = sum(h.out_channels for _, h in heads[:first])              # first channel of the 3d_offset head
-                    edge = self._edge_fusion_at_pois(at_extra.transpose(1, 2), edge_lin, edge_valid, centers_lin)     # B x M x 2
-                    reg_pois = reg_pois + F.pad(edge, (ch0, reg_pois.shape[2] - ch0 - edge.shape[2]))
-                    output_cls = self._edge_fusion_cls(feature_cls, output_cls, targets, edge_cls_feature)
-                output_cls = sigmoid_hm(output_cls)
-                return {'cls': output_cls.float(), 'reg': None, 'reg_pois': reg_pois}
-            moments = trunk_moments.trunks_at(reg_inputs[0], self.reg_features, centers_lin, extra)
+        if cells is not None:
+            output_cls = self._edge_fusion_cls(feature_cls, output_cls, cells, at_edges)
+        return sigmoid_hm(output_cls).float()
+
+    def _trunks_at(self, route, reg_inputs, centers_lin, cells):
+        """Every trunk at centers_lin (B, M) -> (at_centres: (T, B, M, C) or a list of T (B, M, C), at_edge: the 3d_offset trunk at
+        the edge cells (B, K, C) or None).  BN + ReLU run at those positions only: no dense output map where the route allows it."""
+        extra = None if cells is None else (self.offset_index[0], cells.lin)
+        if route == "frozen":
+            return trunk_moments.trunks_at_frozen(reg_inputs[0], self.reg_features, centers_lin, extra)
+        if route == "moments":
+            return trunk_moments.trunks_at(reg_inputs[0], self.reg_features, centers_lin, extra, stacked=True)
+        b, M = centers_lin.shape
+        at_centres, at_edge = [], None
         for i, feat_layer in enumerate(self.reg_features):
-            fused = i == self.offset_index[0] and self.enable_edge_fusion
-            pos = torch.cat((centers_lin, edge_lin), dim=1) if fused else centers_lin
+            fused = cells is not None and i == self.offset_index[0]
+            pos = torch.cat((centers_lin, cells.lin), dim=1) if fused else centers_lin
             conv, norm = feat_layer[0], feat_layer[1]
-            if moments is not None:
-                at_all = moments[i]
-            elif hasattr(norm, "forward_at") and isinstance(feat_layer[2], nn.Identity):
-                at_all = norm.forward_at(conv(reg_inputs[i]), pos)                           # B x N x 256
+            if hasattr(norm, "forward_at") and isinstance(feat_layer[2], nn.Identity):
+                at = norm.forward_at(conv(reg_inputs[i]), pos)                               # B x N x 256
             else:                                                                             # GN / leaky-relu configurations
-                at_all = select_point_of_interest(b, pos, feat_layer(reg_inputs[i]))
-            at = at_all[:, :M].reshape(b * M, self.head_conv)
-            for j, out_head in enumerate(self.reg_heads[i]):
-                o = F.linear(at, out_head.weight.view(out_head.out_channels, self.head_conv), out_head.bias).view(b, M, -1)
-                if fused and j == self.offset_index[1]:
-                    o = o + self._edge_fusion_at_pois(at_all[:, M:].transpose(1, 2), edge_lin, edge_valid, centers_lin)
-                    # the class map gets its edge term densely (it is consumed densely by the focal loss)
-                    output_cls = self._edge_fusion_cls(feature_cls, output_cls, targets, edge_cls_feature)
-                outs.append(o)
-        output_cls = sigmoid_hm(output_cls)
-        return {'cls': output_cls.float(), 'reg': None, 'reg_pois': torch.cat(outs, dim=2).float()}
+                at = select_point_of_interest(b, pos, feat_layer(reg_inputs[i]))
+            if fused:
+                at, at_edge = at[:, :M], at[:, M:]
+            at_centres.append(at)
+        return at_centres, at_edge
 
-    def _head_rows_ok(self):
-        """The shapes ops.head_rows takes: 1x1 output layers over a trunk of at most 256 channels, at most 16 heads."""
+    def _heads(self, at_centres, at_edge, centers_lin, cells, rows):
+        """`reg_pois` (B, M, 415) from the trunks at the centres; rows: every 1x1 output layer in ONE launch (ops.head_rows)
+        instead of a GEMM per head, their concatenation and -- backward -- two GEMMs, a bias sum and a slice copy per head."""
+        b, M = centers_lin.shape
         heads = [h for hs in self.reg_heads for h in hs]
-        return (len(heads) <= 16 and len(self.reg_features) <= 16 and self.head_conv <= 256 and self.head_conv % 4 == 0
-                and all(isinstance(h, nn.Conv2d) and h.kernel_size == (1, 1) and h.groups == 1 and h.in_channels == self.head_conv
-                        for h in heads) and sum(h.out_channels for h in heads) <= 1024)
+        if rows:
+            reg_pois = ops.head_rows(at_centres.reshape(len(self.reg_features), b * M, self.head_conv), self.head_trunk,
+                                     [h.weight for h in heads], [h.bias for h in heads]).view(b, M, -1)
+        else:
+            at_centres = list(at_centres)             # a stacked tensor is unbound once: one stack in the backward
+            reg_pois = torch.cat([F.linear(at_centres[i].reshape(b * M, self.head_conv), h.weight.view(h.out_channels, self.head_conv),
+                                           h.bias).view(b, M, -1) for i, h in zip(self.head_trunk, heads)], dim=2)
+        if cells is not None:
+            edge = self._edge_fusion_at_pois(at_edge.transpose(1, 2), cells, centers_lin)    # B x M x 2
+            reg_pois = reg_pois + F.pad(edge, (self.offset_channel, reg_pois.shape[2] - self.offset_channel - edge.shape[2]))
+        return reg_pois.float()
 
-    def _edge_fusion_cls(self, feature_cls, output_cls, targets, gathered=None):
-        """The class-map half of `_edge_fusion` (dense: the focal loss reads every cell).  gathered: feature_cls at the border
-        cells (B, K, C) when the caller already has it (ops.head_out_and_gather)."""
-        b = feature_cls.shape[0]
-        edge_indices = stack_field(targets, "edge_indices")
-        edge_lens = stack_field(targets, "edge_len").view(b, 1)
-        K = edge_indices.shape[1]
-        bi = torch.arange(b, device=edge_indices.device).view(b, 1, 1)
-        yi = edge_indices[:, :, 1].long().view(b, 1, K)
-        xi = edge_indices[:, :, 0].long().view(b, 1, K)
-        valid = torch.arange(K, device=edge_indices.device).view(1, K) < edge_lens
-        if feature_cls.is_cuda and output_cls.dtype == torch.float32 and output_cls.is_contiguous():
-            # gather / scatter-add at linear cell indices on the HIP kernels (one launch each)
-            lin = (yi * feature_cls.shape[3] + xi).view(b, K)
-            at_edges = gathered if gathered is not None else ops.select_point_of_interest(b, lin, feature_cls)
-            edge_cls_output = self.trunc_heatmap_conv(at_edges.transpose(1, 2))
-            vals = (edge_cls_output * valid.unsqueeze(1).to(edge_cls_output.dtype)).transpose(1, 2)
-            return ops.scatter_add_at(output_cls, vals, lin)
-        ci = torch.arange(self.head_conv, device=feature_cls.device).view(1, -1, 1)
-        edge_cls_output = self.trunc_heatmap_conv(feature_cls[bi, ci, yi, xi])
-        valid = valid.to(edge_cls_output.dtype)
-        co = torch.arange(output_cls.shape[1], device=output_cls.device).view(1, -1, 1)
-        output_cls.index_put_((bi, co, yi, xi), edge_cls_output * valid.unsqueeze(1), accumulate=True)
-        return output_cls
+    def _forward_sparse(self, features, targets, cells):
+        """Training forward with the regression heads evaluated at the object centres only."""
+        centers = stack_field(targets, "target_centers")              # B x M x 2 (x, y)
+        centers_lin = centers[:, :, 1].long() * features.shape[3] + centers[:, :, 0].long()  # B x M
+        route, rows = self._sparse_route(features)
+        feat_cls_in, reg_inputs = self._trunk_inputs(features, route)
+        output_cls = self._class_branch(feat_cls_in, cells, gather_node=True)
+        at_centres, at_edge = self._trunks_at(route, reg_inputs, centers_lin, cells)
+        return {'cls': output_cls, 'reg': None, 'reg_pois': self._heads(at_centres, at_edge, centers_lin, cells, rows)}
 
-    def _forward_sparse_eval(self, features, targets):
+    def _forward_sparse_eval(self, features, cells):
         """Inference forward with the regression heads at the top-K cells only (see `sparse_eval_heads`)."""
-        from dcd_amd.model.layers.utils import select_topk
-        feature_cls = self.class_head[:-1](features)
-        output_cls = self.class_head[-1](feature_cls)
-        b = feature_cls.shape[0]
-        if self.enable_edge_fusion:
-            output_cls = self._edge_fusion_cls(feature_cls, output_cls, targets)
-        heat = sigmoid_hm(output_cls).float()
+        heat = self._class_branch(features, cells, gather_node=False)
         topk = select_topk(heat, K=self.max_detection, fuse_nms=True)                 # scores, cell index, classes, ys, xs: (B, K) each
-        reg_pois = self._heads_at(features, targets, topk[1].long().view(b, -1))
-        return {'cls': heat, 'reg': None, 'reg_pois': reg_pois, 'topk': topk}
+        return {'cls': heat, 'reg': None, 'reg_pois': self._heads_at(features, cells, topk[1]), 'topk': topk}
 
     def _sparse_eval_refusal(self, features):
         """Why the heads cannot be evaluated at chosen cells on this input, or None: the conditions `forward` puts before
@@ -353,7 +370,7 @@ class _predictor(nn.Module):
             return "the features are %s on %s (float32 on the GPU only)" % (features.dtype, features.device)
         if torch.is_grad_enabled():
             return "gradients are enabled (call it under torch.no_grad())"
-        if not self._head_rows_ok():
+        if not self.head_rows_ok:
             return "the output layers are not the 1x1 convolutions ops.head_rows takes"
         if not trunk_moments.frozen(self.reg_features, features):
             return "the trunks are not 3x3 conv + BatchNorm in eval mode + ReLU"
@@ -370,36 +387,20 @@ class _predictor(nn.Module):
         why = self._sparse_eval_refusal(features)
         if why is not None:
             raise NotImplementedError("heads_at: " + why)
-        return self._heads_at(features, targets, centers_lin.long().view(features.shape[0], -1))
+        return self._heads_at(features, self._edge_cells(targets, features.shape[3]), centers_lin)
 
-    def _heads_at(self, features, targets, centers_lin):
-        b, w = features.shape[0], features.shape[3]
-        M = centers_lin.shape[1]
-        extra = None
-        if self.enable_edge_fusion:
-            edge_indices = stack_field(targets, "edge_indices")
-            edge_lens = stack_field(targets, "edge_len").view(b, 1)
-            K = edge_indices.shape[1]
-            edge_lin = edge_indices[:, :, 1].long() * w + edge_indices[:, :, 0].long()
-            edge_valid = torch.arange(K, device=edge_lin.device).view(1, K) < edge_lens
-            extra = (self.offset_index[0], edge_lin)
-        at_centres, at_extra = trunk_moments.trunks_at_frozen(features, self.reg_features, centers_lin, extra)
-        heads = [(i, hd) for i, hs in enumerate(self.reg_heads) for hd in hs]
-        reg_pois = ops.head_rows(at_centres.reshape(len(self.reg_features), b * M, self.head_conv), [i for i, _ in heads],
-                                 [hd.weight for _, hd in heads], [hd.bias for _, hd in heads]).view(b, M, -1)
-        if self.enable_edge_fusion:
-            first = sum(len(hs) for hs in self.reg_heads[:self.offset_index[0]]) + self.offset_index[1]
-            ch0 = sum(hd.out_channels for _, hd in heads[:first])
-            edge = self._edge_fusion_at_pois(at_extra.transpose(1, 2), edge_lin, edge_valid, centers_lin)
-            reg_pois = reg_pois + F.pad(edge, (ch0, reg_pois.shape[2] - ch0 - edge.shape[2]))
-        return reg_pois.float()
+    def _heads_at(self, features, cells, centers_lin):
+        centers_lin = centers_lin.long().view(features.shape[0], -1)
+        at_centres, at_edge = self._trunks_at("frozen", [features], centers_lin, cells)
+        return self._heads(at_centres, at_edge, centers_lin, cells, rows=True)
 
     def forward(self, features, targets):
+        cells = self._edge_cells(targets, features.shape[3])
         if (self.training and self.sparse_training_heads and targets is not None and self.exact_edge_gather
                 and self.output_width == features.shape[3] and self.output_height == features.shape[2]):
-            return self._forward_sparse(features, targets)
+            return self._forward_sparse(features, targets, cells)
         if self.sparse_eval_heads and self._sparse_eval_refusal(features) is None:
-            return self._forward_sparse_eval(features, targets)
+            return self._forward_sparse_eval(features, cells)
         feat_cls_in = self.cls_head_pre(features) if self.deeper_head else features
         feature_cls = self.class_head[:-1](feat_cls_in)
         output_cls = self.class_head[-1](feature_cls)
@@ -411,11 +412,10 @@ class _predictor(nn.Module):
             for j, out_head in enumerate(self.reg_heads[i]):
                 output_reg = out_head(reg_feature)
                 if self.enable_edge_fusion and i == self.offset_index[0] and j == self.offset_index[1]:
-                    self._edge_fusion(feature_cls, reg_feature, output_cls, output_reg, targets)
+                    self._edge_fusion(feature_cls, reg_feature, output_cls, output_reg, targets, cells)
                 output_regs.append(output_reg)
 
-        output_cls = sigmoid_hm(output_cls)
-        return {'cls': output_cls.float(), 'reg': torch.cat(output_regs, dim=1).float()}
+        return {'cls': sigmoid_hm(output_cls).float(), 'reg': torch.cat(output_regs, dim=1).float()}
 
 
 def make_predictor(cfg, in_channels):

@@ -237,29 +237,36 @@ def patch_moments(x, positions=None):
     return S1, G, P
 
 
-def usable(trunks, x):
-    """The eleven-trunk shape this path implements: Sequential(3x3 conv stride 1 pad 1 without bias, fused-ReLU BatchNorm2d, Identity)."""
+def _trunk_shape(trunks, x):
+    """The eleven-trunk shape both forms below implement: Sequential(3x3 conv stride 1 pad 1 without bias, fused-ReLU BatchNorm2d
+    with running statistics, activation slot) on a float 4-D input of the convolutions' width."""
     from dcd_amd.model.layers.norm import BatchNorm2d
-    if not ENABLED or x.dim() != 4 or x.dtype not in (torch.float32, torch.float64):
-        return False
-    for t in trunks:
-        conv, bn = t[0], t[1]
-        if not (isinstance(bn, BatchNorm2d) and bn.fuse_relu and bn.training and bn.momentum is not None and bn.track_running_stats
-                and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-                and conv.groups == 1 and conv.bias is None and conv.in_channels == x.shape[1]):
-            return False
-    return True
+    return (x.dim() == 4 and x.dtype in (torch.float32, torch.float64) and all(
+        isinstance(bn, BatchNorm2d) and bn.fuse_relu and bn.track_running_stats
+        and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+        and conv.groups == 1 and conv.bias is None and conv.in_channels == x.shape[1] for conv, bn in ((t[0], t[1]) for t in trunks)))
 
 
-_TAPS = {}
+def usable(trunks, x):
+    """`trunks_at` applies: the switch is on and the trunks' BatchNorm layers are in training mode."""
+    return ENABLED and _trunk_shape(trunks, x) and all(t[1].training and t[1].momentum is not None for t in trunks)
 
 
-def _taps(W, device):
-    """Offsets of the nine taps inside the padded plane, cached per (width, device): no host-to-device copy per step."""
-    key = (W, str(device))
-    if key not in _TAPS:
-        _TAPS[key] = torch.tensor([dy * (W + 2) + dx for dy in range(3) for dx in range(3)], device=device)
-    return _TAPS[key]
+def _patch_gather(x):
+    """x (B, C, H, W) -> the function pos (B, n) linear pixel indices -> zero-padded 3x3 patches at those cells (B, 9C, n), row
+    c*9 + tap: read straight from the padded input, so that their backward is a scatter of a few thousand values into dx."""
+    B, C, H, W = x.shape
+    xp = F.pad(x, (1, 1, 1, 1)).flatten(2)                                                     # (B, C, (H+2)(W+2))
+    # offsets of the nine taps inside the padded plane, cached per (width, device): no host-to-device copy per step
+    taps = _const(("taps", W, str(x.device)), lambda: torch.tensor([dy * (W + 2) + dx for dy in range(3) for dx in range(3)], device=x.device))
+
+    def patches(pos):
+        pos = pos.long()
+        base = (pos // W) * (W + 2) + pos % W                                                  # top-left of the 3x3 window in xp
+        n = pos.shape[1]
+        idx = (base.unsqueeze(1) + taps.view(1, 9, 1)).reshape(B, 1, 9 * n).expand(B, C, 9 * n)
+        return xp.gather(2, idx).reshape(B, 9 * C, n)                                          # (B, C, 9, n) -> (B, 9C, n)
+    return patches
 
 
 _FUSED_STATS = os.environ.get("DCD_TRUNK_STATS_KERNELS", "1") != "0"       # 0: the finalisation as tensor operations (A/B timing)
@@ -409,7 +416,7 @@ def trunks_at(x, trunks, centers, extra=None, stacked=False):
     B, C, H, W = x.shape
     T = len(trunks)
     pos_all = centers.long() if extra is None else torch.cat((centers.long(), extra[1].long()), dim=1)
-    S1, G, P_all = patch_moments(x, pos_all if os.environ.get("DCD_TRUNK_PATCH_NODE", "1") != "0" else None)   # 0: separate gather (A/B)
+    S1, G, P_all = patch_moments(x, pos_all)
     K = S1.shape[0]
     Wall = torch.stack([t[0].weight.reshape(t[0].out_channels, K) for t in trunks])            # (T, O, 9C)
     n = B * H * W
@@ -460,28 +467,17 @@ def trunks_at(x, trunks, centers, extra=None, stacked=False):
     scale, shift = scale.to(x.dtype), shift.to(x.dtype)
     # patches at the listed positions straight from the (zero-padded) input, not from U: their backward is then a scatter of a
     # few thousand values into dx instead of a zero-filled (B, 9C, HW) tensor, a scatter into it and one more full-size addition
+    M0 = centers.shape[1]
     if P_all is not None:                                      # gathered inside the correlation node (its backward scatters into dx)
-        M0 = centers.shape[1]
-
-        def patches(pos, first):
-            return P_all[:, :, :M0] if first else P_all[:, :, M0:]
-    else:
-        xp = F.pad(x, (1, 1, 1, 1)).flatten(2)                                                 # (B, C, (H+2)(W+2))
-        taps = _taps(W, x.device)
-
-        def patches(pos, first):                                                               # (B, n) -> (B, 9C, n), row c*9 + tap
-            pos = pos.long()
-            base = (pos // W) * (W + 2) + pos % W                                              # top-left of the 3x3 window in xp
-            n = pos.shape[1]
-            idx = (base.unsqueeze(1) + taps.view(1, 9, 1)).reshape(B, 1, 9 * n).expand(B, C, 9 * n)
-            return xp.gather(2, idx).reshape(B, K, n)                                          # (B, C, 9, n) -> (B, 9C, n)
-    Xc = patches(centers, True)                                                                # (B, 9C, M)
-    y = torch.einsum('bkm,tok->tbmo', Xc, Wall)
+        Xc, Xe = P_all[:, :, :M0], P_all[:, :, M0:]
+    else:                                                      # the bmm form has no such node
+        patches = _patch_gather(x)
+        Xc, Xe = patches(centers), patches(extra[1]) if extra is not None else None
+    y = torch.einsum('bkm,tok->tbmo', Xc, Wall)                                                # Xc (B, 9C, M)
     at_centres = _AffineRelu.apply(y, scale, shift)
     at_extra = None
     if extra is not None:
-        i, pos = extra
-        Xe = patches(pos, False)
+        i = extra[0]
         ye = _PatchLinear.apply(Xe, Wall[i]) if x.is_cuda else torch.einsum('bkm,ok->bmo', Xe, Wall[i])
         at_extra = _AffineRelu.apply(ye.unsqueeze(0), scale[i:i + 1], shift[i:i + 1])[0]
     if stacked:
@@ -495,16 +491,7 @@ def trunks_at(x, trunks, centers, extra=None, stacked=False):
 def frozen(trunks, x):
     """The eleven-trunk shape with the BatchNorm layers in EVAL mode (running statistics: the --generate_for_GMW pass freezes
     them, DGDE/engine/trainer.py:62-67, and inference uses them): `trunks_at_frozen` then needs no statistics at all."""
-    from dcd_amd.model.layers.norm import BatchNorm2d
-    if x.dim() != 4 or x.dtype not in (torch.float32, torch.float64):
-        return False
-    for t in trunks:
-        conv, bn = t[0], t[1]
-        if not (isinstance(bn, BatchNorm2d) and bn.fuse_relu and not bn.training and bn.track_running_stats
-                and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-                and conv.groups == 1 and conv.bias is None and conv.in_channels == x.shape[1] and isinstance(t[2], torch.nn.Identity)):
-            return False
-    return True
+    return _trunk_shape(trunks, x) and all(not t[1].training and isinstance(t[2], torch.nn.Identity) for t in trunks)
 
 
 def trunks_at_frozen(x, trunks, centers, extra=None):
@@ -521,15 +508,7 @@ def trunks_at_frozen(x, trunks, centers, extra=None):
     beta = torch.stack([t[1].bias for t in trunks]).to(x.dtype)
     scale = gamma * torch.rsqrt(rv + trunks[0][1].eps)
     shift = beta - rm * scale
-    xp = F.pad(x, (1, 1, 1, 1)).flatten(2)                                                     # (B, C, (H+2)(W+2))
-    taps = _taps(W, x.device)
-
-    def patches(pos):                                                                          # (B, n) -> (B, 9C, n), row c*9 + tap
-        pos = pos.long()
-        base = (pos // W) * (W + 2) + pos % W
-        n = pos.shape[1]
-        idx = (base.unsqueeze(1) + taps.view(1, 9, 1)).reshape(B, 1, 9 * n).expand(B, C, 9 * n)
-        return xp.gather(2, idx).reshape(B, K, n)
+    patches = _patch_gather(x)
     y = torch.einsum('bkm,tok->tbmo', patches(centers), Wall)
     at_centres = torch.relu(y * scale.view(T, 1, 1, -1) + shift.view(T, 1, 1, -1))
     at_extra = None
