@@ -185,6 +185,7 @@ SIGNATURES = {
                               + [c_int, c_int, c_void_p, c_size_t]),
     "dcd_depth_estimates": (c_int, [c_void_p] * 8 + [ctypes.POINTER(DecodeArgs), c_void_p]),
     "dcd_depth_accumulate": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), c_int, c_int, c_void_p, c_void_p]),
+    "dcd_nms_detections": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_double, c_double, c_int] + [c_void_p] * 5),
 }
 
 STATUS = {1: "bad argument", 2: "workspace too small", 3: "kernel launch failed"}

@@ -40,6 +40,7 @@
 #include <stdint.h>
 
 #include "../../include/dcd_hip.h"
+#include "nms_math.h"      // rbbox_to_corners, clipped_area: the one copy of the clip, shared with nms.hip
 
 namespace {
 
@@ -47,54 +48,6 @@ constexpr int WAVE = 64;
 constexpr int OVL_THREADS = 256;
 constexpr int MAX_DT_BLOCKS = 64;               // bits of the per-lane `assigned` mask
 constexpr double NO_DETECTION = -10000000.0;    // eval.py:182
-
-// ---- rotated rectangles, float32 -------------------------------------------------------------------------------------
-// Corners of a rectangle in the reference's order and rotation sense (rbbox_to_corners, rotate_iou.py:207-230).
-__device__ inline void rbbox_to_corners(float *x, float *y, float cx, float cy, float xd, float yd, float a_cos, float a_sin)
-{
-    const float px[4] = {-xd / 2, -xd / 2, xd / 2, xd / 2}, py[4] = {-yd / 2, yd / 2, yd / 2, -yd / 2};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[i] = a_cos * px[i] + a_sin * py[i] + cx;
-        y[i] = -a_sin * px[i] + a_cos * py[i] + cy;
-    }
-}
-
-// Area of the quadrilateral (x, y)[0..3] inside the axis-aligned rectangle |x| <= hx, |y| <= hy: Sutherland-Hodgman against
-// the four sides, then the shoelace sum.  A convex polygon gains at most one vertex per side, so 8 slots hold it; the guard
-// keeps a ninth from ever being written whatever rounding does.  Points on a side count as inside, and a crossing is put
-// exactly on the side, so boxes that touch give a degenerate polygon of area exactly 0 and coincident boxes the full area.
-__device__ float clipped_area(float *x, float *y, float hx, float hy)
-{
-    float ox[8], oy[8];
-    int n = 4;
-    for (int side = 0; side < 4; ++side) {
-        const bool along_x = side < 2;
-        const float sgn = (side & 1) ? -1.f : 1.f, lim = along_x ? hx : hy;       // inside: sgn * coordinate <= lim
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            const int k = i + 1 == n ? 0 : i + 1;
-            const float pi = sgn * (along_x ? x[i] : y[i]), pk = sgn * (along_x ? x[k] : y[k]);
-            const bool in_i = pi <= lim, in_k = pk <= lim;
-            if (in_i && m < 8) { ox[m] = x[i]; oy[m] = y[i]; ++m; }
-            if (in_i != in_k && m < 8) {
-                const float t = (lim - pi) / (pk - pi);
-                ox[m] = along_x ? sgn * lim : x[i] + t * (x[k] - x[i]);
-                oy[m] = along_x ? y[i] + t * (y[k] - y[i]) : sgn * lim;
-                ++m;
-            }
-        }
-        n = m;
-        if (n < 3) return 0.f;
-        for (int i = 0; i < n; ++i) { x[i] = ox[i]; y[i] = oy[i]; }
-    }
-    float twice = 0.f;
-    for (int i = 0; i < n; ++i) {
-        const int k = i + 1 == n ? 0 : i + 1;
-        twice += x[i] * y[k] - x[k] * y[i];
-    }
-    return fabsf(twice) / 2.0f;
-}
 
 // image of pair p: the last i with pair_off[i] <= p
 __device__ inline int image_of_pair(const int64_t *__restrict__ pair_off, int n_img, int64_t p)

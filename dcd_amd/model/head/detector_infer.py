@@ -34,6 +34,7 @@ class PostProcessor(nn.Module):
         self.uncertainty_as_conf, self.generate_data = test.UNCERTAINTY_AS_CONFIDENCE, test.GENERATE_GMW
         self.extra_kpts_num, self.output_depth = head.EXTRA_KPTS_NUM, head.OUTPUT_DEPTH
         self.img_width = cfg.INPUT.WIDTH_TRAIN
+        self.nms_mode, self.nms_thresh, self.nms_class_agnostic = self._nms_settings(test)
         heads = set(key2channel.keys)
         self.pred_direct_depth = 'depth' in heads
         self.depth_with_uncertainty = 'depth_uncertainty' in heads
@@ -45,6 +46,22 @@ class PostProcessor(nn.Module):
         self._host_stats = (tuple(tuple(float(v) for v in row) for row in head.DIMENSION_MEAN),
                             tuple(tuple(float(v) for v in row) for row in head.DIMENSION_STD),
                             tuple(float(v) for v in head.DEPTH_REFERENCE))
+
+    @staticmethod
+    def _nms_settings(test):
+        """TEST.USE_NMS / NMS_THRESH / NMS_CLASS_AGNOSTIC, checked (DESIGN.md "Box NMS").  'none' looks at nothing else."""
+        mode = test.USE_NMS
+        if mode == 'none':
+            return 'none', None, bool(test.NMS_CLASS_AGNOSTIC)
+        if mode not in ('2d', 'bev', '3d'):
+            raise ValueError("TEST.USE_NMS %r: one of 'none', '2d', 'bev', '3d'" % (mode,))
+        thresh = float(test.NMS_THRESH)
+        if not 0.0 <= thresh < 1.0:
+            raise ValueError("TEST.USE_NMS %r needs 0 <= TEST.NMS_THRESH < 1 (got %r)" % (mode, test.NMS_THRESH))
+        if test.DETECTIONS_PER_IMG > 128:
+            raise ValueError("TEST.USE_NMS %r takes at most 128 detections per image (TEST.DETECTIONS_PER_IMG %d)"
+                             % (mode, test.DETECTIONS_PER_IMG))
+        return mode, thresh, bool(test.NMS_CLASS_AGNOSTIC)
 
     _OPTIONAL_FIELDS = ("cls_ids", "target_centers", "dimensions", "rotys", "locations", "offset_3D", "extra_kpts_2d",
                         "extra_kpts_3d", "reg_mask", "Calib_P")
@@ -80,7 +97,8 @@ class PostProcessor(nn.Module):
             return None
         centres = torch.stack((xs.view(-1), ys.view(-1)), dim=1)
         return {"scores": scores[keep], "classes": classes.view(-1)[keep], "centres": centres[keep], "vectors": vectors[keep],
-                "image_of": torch.div(keep, per_image, rounding_mode="floor")}
+                "image_of": torch.div(keep, per_image, rounding_mode="floor"), "slot": keep, "blocks": scores.numel() // per_image,
+                "per_image": per_image}
 
     @staticmethod
     def _nothing_detected(like, vis):
@@ -192,7 +210,38 @@ class PostProcessor(nn.Module):
         rows = torch.cat([det["classes"].view(-1, 1), alphas, dec["box2d"], dims_hwl, locations, rotys, scores], dim=1)
         info = {'dis_ious': None, 'depth_errors': None, 'uncertainty_conf': confidence, 'estimated_depth_error': depth_error,
                 'vis_scores': raw_scores}
+        if self.nms_mode != 'none':
+            rows, rows_image = self._nms_kept_rows(det, rows, raw_scores, info, vis, rows_image)
         return (rows, info, vis, rows_image) if batched else (rows, info, vis)
+
+    _DENSE_VIS = ('heat_map', 'depth_uncertainty')           # whole maps: the only tensors of `vis` that are not one entry per row
+
+    def _nms_kept_rows(self, det, rows, raw_scores, info, vis, rows_image):
+        """The op-by-op routes' NMS: the kept rows go back to the (B, K) blocks they were cut from (every other slot with a NaN raw
+        score, which ends the block's prefix), the batched pass's kernel runs on them, and the survivors -- the prefix of every
+        output block -- are read off.  The source slot of a row travels in aux[:, 3].  Every tensor of `info` and `vis` other
+        than the dense maps is one entry per row and follows the same selection; one that is not (a key added later with another
+        layout) is an error here, not a table that silently keeps the rows from before the NMS."""
+        from dcd_amd import ops
+        B, K, slot = det["blocks"], det["per_image"], det["slot"]
+        rows_blk = rows.new_zeros((B * K, 14))
+        aux_blk = rows.new_zeros((B * K, 4))
+        aux_blk[:, 0] = float("nan")
+        rows_blk[slot] = rows.float()
+        aux_blk[slot, 0] = raw_scores.view(-1).float()
+        aux_blk[slot, 3] = torch.arange(rows.shape[0], device=rows.device, dtype=torch.float32)
+        _, aux_out, _, _, _ = ops.nms_detections(rows_blk, aux_blk, None, None, K, self.nms_mode, self.nms_thresh, self.det_threshold,
+                                                 self.nms_class_agnostic)
+        sel = aux_out[aux_out[:, 0] >= self.det_threshold, 3].long()       # (image, rank) order: blocks in order, survivors in rank order
+        for table in (info, vis):
+            for k, v in table.items():
+                if not torch.is_tensor(v) or k in self._DENSE_VIS:
+                    continue
+                if v.dim() == 0 or v.shape[0] != rows.shape[0]:
+                    raise RuntimeError("PostProcessor NMS: %r is %s, neither a dense map nor one entry per row (%d rows)"
+                                       % (k, tuple(v.shape), rows.shape[0]))
+                table[k] = v[sel]
+        return rows[sel], (None if rows_image is None else rows_image[sel])
 
     # ---- the whole decode in one launch (csrc/decode.hip) ---------------------------------------------------------------
     _FUSED_HEADS = ('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth',
@@ -259,6 +308,9 @@ class PostProcessor(nn.Module):
         table = self._image_table(targets, vectors.device)
         want = self.generate_data if records is None else bool(records)
         rows, aux, k2, k3 = ops.decode_detections(vectors, topk, table, spec, records=want)
+        if self.nms_mode != 'none':                           # one more launch; the outputs keep the prefix contract
+            rows, aux, k2, k3, _ = ops.nms_detections(rows, aux, k2, k3, topk[0].shape[1], self.nms_mode, self.nms_thresh,
+                                                      self.det_threshold, self.nms_class_agnostic)
         return rows, aux, ((k2, k3) if want else None)
 
     def _image_kpts(self, targets, pois, pred_bbox_points, pred_offset_3D):

@@ -2008,6 +2008,43 @@ def decode_detections(vectors, topk, image_table, spec, records=False):
     return rows, aux, k2, k3
 
 
+NMS_MODE = {"2d": 1, "bev": 2, "3d": 3}
+NMS_MAX_K = 128
+
+
+def nms_detections(rows, aux, k2, k3, K, mode, thresh, det_threshold, class_agnostic, want_overlaps=False):
+    """Greedy box NMS among the candidates of every image of a batch in ONE launch (csrc/nms.hip; the rule is in DESIGN.md "Box
+    NMS" and include/dcd_hip.h): rows (B K, 14), aux (B K, 4), k2 (B K, nk, 2) / k3 (B K, nk, 3) or None -- the outputs of
+    `decode_detections`.  Returns compacted copies (rows, aux, k2, k3, overlaps): per image block the survivors in rank order,
+    then the suppressed rows with a raw score aux[:, 0] of -inf, then the rows below `det_threshold`, so the prefix
+    `aux[:, 0] >= det_threshold` of a block is its survivors.  overlaps: (B, K, K) fp32 of what was compared, or None.
+    No host synchronisation."""
+    _lib.require_cuda(rows, aux, k2, k3)
+    if mode not in NMS_MODE:
+        raise ValueError("NMS mode %r (one of %s)" % (mode, ", ".join(sorted(NMS_MODE))))
+    if (k2 is None) != (k3 is None):
+        raise ValueError("both key-point tensors or neither")
+    K = int(K)
+    rows, aux = _f32c(rows).reshape(-1, 14), _f32c(aux).reshape(-1, 4)
+    n = rows.shape[0]
+    if K < 1 or n % K or aux.shape[0] != n:
+        raise ValueError("rows %s and aux %s do not hold blocks of K = %d" % (tuple(rows.shape), tuple(aux.shape), K))
+    nk = 0
+    if k2 is not None:
+        k2, k3 = _f32c(k2), _f32c(k3)
+        nk = k2.shape[1]
+        if tuple(k2.shape) != (n, nk, 2) or tuple(k3.shape) != (n, nk, 3):
+            raise ValueError("key points %s / %s for %d rows" % (tuple(k2.shape), tuple(k3.shape), n))
+    B = n // K
+    outs = [None if t is None else torch.empty_like(t) for t in (rows, aux, k2, k3)]
+    overlaps = torch.empty((B, K, K), dtype=torch.float32, device=rows.device) if want_overlaps else None
+    st = _lib.lib().dcd_nms_detections(_lib.stream_of(rows), rows.data_ptr(), aux.data_ptr(), _lib.ptr(k2), _lib.ptr(k3), B, K, nk,
+                                       NMS_MODE[mode], float(thresh), float(det_threshold), int(bool(class_agnostic)),
+                                       outs[0].data_ptr(), outs[1].data_ptr(), _lib.ptr(outs[2]), _lib.ptr(outs[3]), _lib.ptr(overlaps))
+    _lib.check(st, "dcd_nms_detections")
+    return outs[0], outs[1], outs[2], outs[3], overlaps
+
+
 DEPTH_METHODS = ("direct", "kpt_center", "kpt_02", "kpt_13", "soft", "hard", "mean", "edges", "oracle", "gmw")
 DEPTH_ROW = 3 + len(DEPTH_METHODS)     # valid, class, gt_z, the methods
 DEPTH_STATS = 5                        # count, sum |e|, sum e, sum e^2, non-finite estimates

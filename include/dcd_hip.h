@@ -967,6 +967,41 @@ int dcd_depth_estimates(void *stream, const float *vectors, const float *ys, con
 int dcd_depth_accumulate(void *stream, const float *est, int n_slots, const float *edges, int n_bins, int num_classes,
                          double *table, int64_t *outside);
 
+/* ------------------------------------------------------------------------------------------------
+ * Box NMS among the decoded candidates of every image of a batch, in ONE launch (csrc/nms.hip, arithmetic in csrc/nms_math.h):
+ * TEST.USE_NMS.  The reference names the configuration keys and never reads them, so the rule is this library's:
+ *   candidates  of image b: the prefix of its block of K rows whose raw score aux[., 0] is >= det_threshold (the raw scores
+ *               leave the top-K descending, so this is every such row; a NaN ends the prefix, as the host's cut does; the
+ *               comparison is float32 against det_threshold rounded to float32, as the host's is)
+ *   order       descending FINAL score rows[., 13]; a tie goes to the lower rank; a NaN score is visited last
+ *   rule        greedy: a candidate is suppressed when its overlap with an already KEPT candidate is > thresh; unless
+ *               class_agnostic, only kept candidates of the same class count -- the integer part of rows[., 0], which is how the
+ *               result writer names a row (the column carries the top-K's fraction).  A suppressed candidate suppresses nothing.
+ *   overlap     KITTI's evaluator's (dcd_eval_overlaps), the kept box in the ground-truth box's role and the visited candidate
+ *               in the detection's: DCD_NMS_2D image_box_overlap, criterion -1, float64, on rows[., 2:6]; DCD_NMS_BEV the clipped
+ *               rotated area in float32 on (x, z, l, w, ry) over the union; DCD_NMS_3D that area times the height overlap from y
+ *               and h over the volume union.  The comparison with thresh is made in float64.
+ *   rows (B K, 14), aux (B K, 4), kpts2d (B K, nk, 2), kpts3d (B K, nk, 3): dcd_decode_detections' outputs; the key points may
+ *               both be NULL (then so are their outputs, and nk is not read)
+ *   rows_out, aux_out, kpts2d_out, kpts3d_out: the same shapes; per image block a permutation of the input rows, bit for bit:
+ *               the survivors in their rank order, then the suppressed rows in rank order, then the rows below the threshold
+ *               where they were.  The raw score aux_out[., 0] of every suppressed row is -inf, so the prefix `score >= threshold`
+ *               of the output block is exactly the survivors.  Outputs must not alias inputs.
+ *   overlaps_out (B, K, K) fp32 or NULL: element (i, j) of an image, i != j both candidates, = the overlap of candidates i and j
+ *               (input ranks) the decision was taken from, with the one visited first in the kept box's role; symmetric;
+ *               every other element 0.  With it every pair is evaluated; without it, class-aware, only pairs of one class.
+ * One workgroup per image; no atomics, no workspace, nothing read back: two calls give the same bits.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null or aliased pointer, B < 1, K outside 1 .. 128, B K > 2^31 - 1, nk outside
+ * 1 .. 128 when key points are given, only some of the four key-point pointers given, an unknown mode, thresh outside [0, 1)
+ * or NaN, or a NaN det_threshold.
+ * ---------------------------------------------------------------------------------------------- */
+#define DCD_NMS_2D 1
+#define DCD_NMS_BEV 2
+#define DCD_NMS_3D 3
+int dcd_nms_detections(void *stream, const float *rows, const float *aux, const float *kpts2d, const float *kpts3d, int B, int K,
+                       int nk, int mode, double thresh, double det_threshold, int class_agnostic, float *rows_out, float *aux_out,
+                       float *kpts2d_out, float *kpts3d_out, float *overlaps_out);
+
 #ifdef __cplusplus
 }
 #endif
