@@ -27,7 +27,8 @@ next to overwrite, while the step still reads it.
 Evaluation over a split has a FINITE plan of its own: `EvalPlan(size, batch_size)` gives batch k = images
 [k B, min((k + 1) B, size)) in file order -- the last batch may be short, nothing wraps around, nothing flips -- and
 `EvalBatches(files, pipeline, batch_size, workers=None)` decodes them in a thread pool; `EvalPrefetcher` is the `Prefetcher` that
-stops at the last batch; `eval_batches(files, pipeline, batch_size, workers=None)` is the two together, as the passes walk them."""
+stops at the last batch; `eval_batches(files, pipeline, batch_size, workers=None, keep_frames=False)` is the two together, as the
+passes walk them; `keep_frames` is the pipeline's keyword: the targets then carry the staged uint8 frames for the renderer."""
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -171,10 +172,11 @@ class EvalBatches:
     """`get(k) -> (images, targets)` of `EvalPlan`'s batch k through a `DeviceInputPipeline(is_train=False)`; the frames are read
     and decoded by `default_workers(workers)` threads."""
 
-    def __init__(self, files, pipeline, batch_size, workers=None):
+    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False):
         if pipeline.is_train:
             raise ValueError("evaluation needs a DeviceInputPipeline(is_train=False): it never flips")
         self.files, self.pipeline, self.batch_size, self.is_train = files, pipeline, int(batch_size), False
+        self.keep_frames = bool(keep_frames)
         self.plan = EvalPlan(len(files), batch_size)
         self._pool = ThreadPoolExecutor(max_workers=default_workers(workers))
 
@@ -191,7 +193,8 @@ class EvalBatches:
     def get(self, k):
         indices, _ = self.plan(k)
         read = list(self._pool.map(self._read, indices))
-        return self.pipeline([f for f, _ in read], [s for _, s in read], img_ids=[self.files.img_id(i) for i in indices])
+        extra = {"keep_frames": True} if self.keep_frames else {}
+        return self.pipeline([f for f, _ in read], [s for _, s in read], img_ids=[self.files.img_id(i) for i in indices], **extra)
 
     def close(self):
         self._pool.shutdown(wait=True)
@@ -213,8 +216,8 @@ class eval_batches:
 
     Leaving the `with` block, by its end or by an exception, shuts the thread pool down."""
 
-    def __init__(self, files, pipeline, batch_size, workers=None):
-        self.source = EvalBatches(files, pipeline, batch_size, workers)
+    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False):
+        self.source = EvalBatches(files, pipeline, batch_size, workers, keep_frames)
         self._batches = EvalPrefetcher(self.source, pipeline.device)
 
     def __enter__(self):

@@ -3,7 +3,7 @@
 `KITTIDataset.__getitem__` would have (DGDE/data/datasets/kitti.py:299-320, :608), with targets that agree with the flipped image.
 
     pipe = DeviceInputPipeline(cfg, device, is_train=True, seed=None)
-    images, targets = pipe(frames, samples, img_ids=None, flip=None, stream=None)
+    images, targets = pipe(frames, samples, img_ids=None, flip=None, stream=None, keep_frames=False)
 
 What runs where: the flip of the label values on the host (dcd_amd/data/augment.py, a few dozen scalars per image), the image
 work -- `RandomHorizontallyFlip`, `pad_image`, `ToTensor`, `Normalize`, `TO_BGR` -- in ONE launch per batch (csrc/images.hip,
@@ -96,7 +96,10 @@ class DeviceInputPipeline:
             np.copyto(view[off:off + a.size].reshape(h, w, 3), a)
         return slot, nbytes
 
-    def __call__(self, frames, samples, img_ids=None, flip=None, stream=None):
+    def __call__(self, frames, samples, img_ids=None, flip=None, stream=None, keep_frames=False):
+        """keep_frames: every target also carries "frames" -- the staged uint8 buffer on the device, `_pack`'s layout, the same
+        tensor for all B -- "frame_records", its (B, 5) int64 record table (a view of its head), and "frame_size", the image's own
+        (w, h) on the host: what `ops.render_detections` draws on.  Without the flag the staged buffer is let go as before."""
         B = len(frames)
         if B == 0 or len(samples) != B:
             raise ValueError("%d frames for %d samples" % (B, len(samples)))
@@ -120,5 +123,11 @@ class DeviceInputPipeline:
                                                self._table.data_ptr(), B, self.in_h, self.in_w, int(self.to_bgr), images.data_ptr()),
                        "dcd_preprocess_images")
             targets = encode_targets([flip_sample(s) if f else s for s, f in zip(samples, flags)], self.cfg, self.device, img_ids)
+            if keep_frames:
+                records = staged[:B * _REC * 8].view(torch.int64).view(B, _REC)
+                for t, f in zip(targets, frames):
+                    t.add_field("frames", staged)
+                    t.add_field("frame_records", records)
+                    t.add_field("frame_size", (int(f.shape[1]), int(f.shape[0])))
         self.last_flip = flags
         return images, targets

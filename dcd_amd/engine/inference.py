@@ -1,7 +1,7 @@
 """From a KITTI directory to the AP table: the use DGDE/engine/inference.py:19-125 makes of the model, the result writer and
 the evaluator.  One image per model call, as the reference runs its evaluation (TEST.IMS_PER_BATCH = 1); every image's
 `PostProcessor` rows go to `<output_folder>/data/<id>.txt`, then the files are read back and evaluated against `label_2`
-on the device.  No visualisation.
+on the device.
 
 With `batch_size > 1` or `gen_out_dir` the split is walked in batches instead (`_batched_pass`): frames decoded by a thread
 pool, batch k + 1 prepared on a side stream while batch k runs, backbone -> predictor (heads at the top-K cells only) ->
@@ -15,8 +15,14 @@ stay on the device, `gmw.RecordRefiner` gathers them into GMW's input layout (`o
 of `gmw_batch`, and after the last batch the refined files go to `<output_folder>/kitti_results_for_eval` and are scored; the
 result is `results["gmw"]`.  No `gen_data_infer.json` lies between the stages.
 
+With `render_dir=` the same pass also leaves `<render_dir>/<id>.png` for every image: the frame with the kept detections' 2-D
+boxes, projected 3-D boxes and labels (with `render_keypoints` the dense key points too) over the ground truth, and a bird's-eye
+panel beside it -- drawn on the device from the decode's outputs and the staged frames (`dcd_amd.engine.render`),
+copied out once per batch and PNG-encoded by a thread pool.  Rows under TEST.DETECTIONS_THRESHOLD, rows an NMS suppressed and rows
+whose score is not above TEST.VISUALIZE_THRESHOLD are not drawn; with `gmw=` the pictures show the detector's rows.
+
     python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
-                                       [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]
+                                       [--gmw-ckpt FILE [--gmw-batch N]] [--render-dir DIR [--render-keypoints]] [KEY VALUE ...]
 
 evaluates a saved checkpoint (or, with --gmw-ckpt, a detector and a GMW checkpoint together) on its own.  `--split test` reads
 `ImageSets/test.txt`, the images and `calib` only and writes one result file per id, in `inference/data` and, with --gmw-ckpt,
@@ -53,12 +59,14 @@ def _records(rows, k2, k3, cat="Car"):
              'score': r[13:14], 'cat': cat} for i, r in enumerate(rows)]
 
 
-def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records, refiner=None):
+def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records, refiner=None, renderer=None):
     """The batched loop.  Returns {img_id: records} (empty without `want_records`).  Raises NotImplementedError, before anything
     runs, when the configuration is one `decode_fused` does not cover.  refiner: a `gmw.RecordRefiner`; the decode then always
     leaves the key points on the device, every batch's kept rows are handed to it (`refiner.add`, a batch late, with the host
     rows appended to `refiner.host_rows` / `refiner.host_ids` for the writer), and the key points go to the host only with
-    `want_records`."""
+    `want_records`.  renderer: a `dcd_amd.engine.render.Renderer`; the walker then keeps the staged frames with the targets and every
+    batch is drawn right after its decode (`renderer.add`); a renderer that draws key points makes the decode leave them on the
+    device as the refiner does."""
     from dcd_amd.data.batches import eval_batches
     pp, predictor = model.heads.post_processor, model.heads.predictor
     spec = pp.decode_spec()                                            # refuses here, before the walker and its threads exist
@@ -92,12 +100,17 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     sparse_before = predictor.sparse_eval_heads
     predictor.sparse_eval_heads = True
     try:
-        with eval_batches(files, pipeline, batch_size, workers) as walk:
+        keep = {"keep_frames": True} if renderer is not None else {}
+        device_records = want_records or refiner is not None or (renderer is not None and renderer.keypoints)
+        with eval_batches(files, pipeline, batch_size, workers, **keep) as walk:
             pending = None
             for k, indices, images, targets in walk:
                 feats = model.backbone(images)
                 preds = predictor(feats, targets)
-                rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=want_records or refiner is not None)
+                rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=device_records)
+                if renderer is not None:
+                    renderer.add(k, [files.img_id(i) for i in indices], targets[0].get_field("frames"), rows, aux, recs,
+                                 pp._image_table(targets, rows.device), targets)
                 n = rows.shape[0]
                 parts = [rows, aux] + ([recs[0].reshape(n, nk * 2), recs[1].reshape(n, nk * 3)] if want_records else [])
                 slots[k % 2][:n].copy_(torch.cat(parts, dim=1), non_blocking=True)
@@ -113,7 +126,7 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
 
 
 def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_size=1, workers=None, gen_out_dir=None, gmw=None,
-              gmw_batch=256):
+              gmw_batch=256, render_dir=None, render_keypoints=False):
     """model: a `KeypointDetector`; files: a `KittiFiles`; pipeline: a `DeviceInputPipeline(is_train=False)`.
     batch_size = 1 and gen_out_dir = None: one image per model call, as the reference.  Otherwise the batched pass (see the
     module docstring); gen_out_dir: where the same pass leaves `gen_data_infer.json`.  A configuration the fused decode does
@@ -123,6 +136,9 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     records), `<output_folder>/kitti_results_for_eval` gets the files of `gmw.write_results` (class "Car", one file per id of
     the split) and their tables are `results["gmw"] = {metric: dict}`.  With `gmw` a configuration the fused decode does not
     cover is an error (NotImplementedError): no other route can feed the second stage.
+    render_dir: where the pass leaves one picture per id, `<render_dir>/<id>.png` (`dcd_amd.engine.render`): the pass is then always
+    the batched one and, as with `gmw`, a configuration the fused decode refuses is an error.  render_keypoints: draw the dense key
+    points as well.  An unlabelled split draws no ground truth.  With render_dir = None nothing of this is launched, allocated or kept.
     Returns {metric: the dict of `kitti_ap.official_eval`}.
     A `files` whose `has_labels` is false (KITTI's `test` split; an object without the attribute counts as labelled) goes through
     the same pass and only leaves its files behind: see `finish_pass`."""
@@ -136,22 +152,33 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     ids = [files.img_id(i) for i in range(len(files))]
     with restored_modes(model, gmw), torch.no_grad():
         model.eval()
-        batched = batch_size > 1 or gen_out_dir is not None or gmw is not None
-        refiner = None
+        batched = batch_size > 1 or gen_out_dir is not None or gmw is not None or render_dir is not None
+        refiner = renderer = None
+        if render_dir is not None:
+            from dcd_amd.engine.render import Renderer
+            renderer = Renderer(model.cfg, pipeline.device, keypoints=render_keypoints,
+                                render_dir=render_dir, workers=workers, labelled=getattr(files, "has_labels", True))
         if gmw is not None:
             from dcd_amd.gmw.inference import RecordRefiner
             gmw.eval()
             refiner = RecordRefiner(gmw, pipeline.device, batch_size=gmw_batch, nk=model.heads.post_processor.extra_kpts_num + 10)
         if batched:
             try:
-                infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
-                                           refiner)
+                extra = {"renderer": renderer} if renderer is not None else {}
+                try:
+                    infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
+                                               refiner, **extra)
+                finally:
+                    if renderer is not None:
+                        renderer.finish()
                 if gen_out_dir is not None:
                     from dcd_amd.engine import gen_data
                     gen_data.dump_gen_data_infer(infer_data, gen_out_dir)
             except NotImplementedError as e:
                 if gmw is not None:
                     raise NotImplementedError("inference(gmw=...) needs the fused decode, which refuses this configuration: %s" % e)
+                if renderer is not None:
+                    raise NotImplementedError("inference(render_dir=...) needs the fused decode, which refuses this configuration: %s" % e)
                 logger.info("batched evaluation is not available (%s): one image per call", e)
                 batched = False
                 if gen_out_dir is not None:
@@ -209,7 +236,7 @@ def finish_pass(files, ids, output_folder, metrics, device, refined=None):
 
 def main(argv=None):
     """`python -m dcd_amd.engine.inference --root KITTI_DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
-    [--gmw-ckpt FILE [--gmw-batch N]] [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
+    [--gmw-ckpt FILE [--gmw-batch N]] [--render-dir DIR [--render-keypoints]] [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
     import argparse
     import json
     from dcd_amd.config import get_cfg
@@ -227,8 +254,13 @@ def main(argv=None):
     ap.add_argument("--gmw-ckpt", default=None, help="a GMW checkpoint (checkpoint_epoch_N.pth.tar of dcd_amd.gmw.train): refine the "
                     "kept detections in the same pass and score the refined files as well")
     ap.add_argument("--gmw-batch", type=int, default=256, help="records per refinement call")
+    ap.add_argument("--render-dir", default=None, help="also leave one picture per image here, <id>.png: detections over ground truth "
+                    "and a bird's-eye panel, drawn on the device in the same pass")
+    ap.add_argument("--render-keypoints", action="store_true", help="with --render-dir: draw the dense key points too")
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
+    if args.render_keypoints and not args.render_dir:
+        ap.error("--render-keypoints needs --render-dir")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
     cfg = get_cfg(opts=parse_overrides(args.opts))
     device = torch.device("cuda", torch.cuda.current_device())
@@ -238,7 +270,8 @@ def main(argv=None):
     pipeline = DeviceInputPipeline(cfg, device, is_train=False)
     gen_out_dir = os.path.join(args.output_dir, "gen_data") if args.gen_data else None
     results = inference(model, files, pipeline, os.path.join(args.output_dir, "inference"), metrics=tuple(cfg.TEST.METRIC),
-                        batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir, gmw=gmw, gmw_batch=args.gmw_batch)
+                        batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir, gmw=gmw, gmw_batch=args.gmw_batch,
+                        render_dir=args.render_dir, render_keypoints=args.render_keypoints)
 
     def plain(v):
         return {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else (v.tolist() if hasattr(v, "tolist") else v)

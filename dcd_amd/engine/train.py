@@ -265,7 +265,7 @@ def collect_gmw_records(model, batches, iterations, start=0, capacity=None, cfg=
 
 
 def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None,
-             val_batch_size=1, val_gmw=None, gmw_records=False):
+             val_batch_size=1, val_gmw=None, gmw_records=False, val_render_dir=None, val_render_keypoints=False):
     """batches: a source of data/batches.py (or a `Prefetcher` around one).  step: `step(images, targets) -> (loss_dict,
     log_loss_dict)`, e.g. a `GraphedTrainStep`; by default `train_step` with SOLVER.GRAD_NORM_CLIP.  val: (files, pipeline) of
     `engine.inference.inference`, run after the final checkpoint; its result comes back as arguments["eval"].
@@ -280,7 +280,9 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     gmw_records (with TEST.GENERATE_GMW only): True collects GMW's training records on the device (`collect_gmw_records`) instead
     of running the loss over the split; arguments["gmw_records"] is then the `ResidentRecords` that `gmw.train.train_gmw` takes,
     and `gen_data_train.json` is not written.  "json" writes the file as well, from one bulk copy.  A configuration the record
-    kernel refuses raises NotImplementedError before the first batch.  False (the default): the pass and the file as before."""
+    kernel refuses raises NotImplementedError before the first batch.  False (the default): the pass and the file as before.
+    val_render_dir: the evaluation also leaves one picture per validation image there (`inference(render_dir=...)`, the batched
+    pass whatever val_batch_size is); val_render_keypoints draws the dense key points too."""
     logger = logging.getLogger("dcd_amd.trainer")
     is_gen = bool(cfg.TEST.GENERATE_GMW)
     if cfg.SOLVER.LR_WARMUP and warmup_scheduler is None:
@@ -358,14 +360,15 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
                     total / max(1, max_iter - start_iter))
     if val is not None:
         from dcd_amd.engine.inference import inference
+        render = {"render_dir": val_render_dir, "render_keypoints": val_render_keypoints} if val_render_dir is not None else {}
         if val_batch_size > 1 or val_gmw is not None:
             gen_out_dir = os.path.join(output_dir, "gen_data") if is_gen else None
             if is_gen:
                 logger.info("Start generate Infer data for GMW (same pass as the evaluation)")
             arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"), batch_size=val_batch_size,
-                                          gen_out_dir=gen_out_dir, gmw=val_gmw)
+                                          gen_out_dir=gen_out_dir, gmw=val_gmw, **render)
         else:
-            arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"))
+            arguments["eval"] = inference(model, val[0], val[1], os.path.join(output_dir, "inference"), **render)
     return arguments
 
 

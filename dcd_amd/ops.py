@@ -2103,3 +2103,124 @@ def depth_accumulate(est, edges, table, outside):
     st = _lib.lib().dcd_depth_accumulate(_lib.stream_of(est), est.data_ptr(), int(est.shape[0]), c_edges, n_bins, num_classes,
                                          table.data_ptr(), outside.data_ptr())
     _lib.check(st, "dcd_depth_accumulate")
+
+
+RENDER_ENTRY = 12          # int32 per primitive: panel, kind, x0, y0, x1, y1, thickness, r, g, b, order, glyph (csrc/render_math.h)
+_FRAME_REC = 5             # int64 per image in front of the staged frames (dcd_amd/data/input_pipeline.py, `_pack`)
+
+
+def stage_frames(frames, device):
+    """A list of (h, w, 3) uint8 RGB arrays -> the staged buffer `DeviceInputPipeline._pack` builds, on `device`: (B, 5) int64
+    records (byte offset, row pitch, height, width, flip = 0), then the frames packed HWC at 64-byte boundaries.  For callers of
+    the renderer that do not come through the input pipeline."""
+    import numpy as np
+    arrays = [np.ascontiguousarray(f.cpu().numpy() if torch.is_tensor(f) else f) for f in frames]
+    B = len(arrays)
+    offsets, nbytes = [], -(-B * _FRAME_REC * 8 // 64) * 64
+    for i, a in enumerate(arrays):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError("frame %d: expected a (h, w, 3) uint8 RGB array, got %s %s" % (i, a.dtype, a.shape))
+        offsets.append(nbytes)
+        nbytes += -(-a.size // 64) * 64
+    host = np.zeros(nbytes, np.uint8)
+    rec = host[:B * _FRAME_REC * 8].view(np.int64).reshape(B, _FRAME_REC)
+    for i, (a, off) in enumerate(zip(arrays, offsets)):
+        rec[i] = (off, 3 * a.shape[1], a.shape[0], a.shape[1], 0)
+        host[off:off + a.size] = a.reshape(-1)
+    return torch.from_numpy(host).to(device)
+
+
+def _staged(frames):
+    staged = frames[0] if isinstance(frames, (tuple, list)) else frames
+    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1 or not staged.is_contiguous():
+        raise ValueError("frames: the staged uint8 buffer of the input pipeline (records in front), or (buffer, records)")
+    return staged
+
+
+def render_slots(M, K, nk):
+    """Entries per image of the renderer's primitive table for M ground-truth slots, K candidates and nk drawn key points."""
+    return int(_lib.lib().dcd_render_slots(int(M), int(K), int(nk)))
+
+
+def render_detections(frames, rows, aux, k2, k3, image_table, gt, K, det_threshold, vis_threshold, keypoints=False, want_table=False,
+                      in_h=None, in_w=None, canvas=None):
+    """The detections of a batch drawn on the device in two launches (csrc/render.hip; the rule is DESIGN.md 6d): returns
+    (canvas (B, in_h, in_w + in_h, 3) uint8, table or None).  The picture of image b, frame w x h, is canvas[b, :h, :w + h]: the
+    frame with 2-D boxes, projected 3-D boxes, labels and -- with `keypoints` -- the nk key points, then the h x h bird's-eye panel.
+    frames: the staged buffer of `DeviceInputPipeline(..., keep_frames=True)` (targets' "frames" field) or of `stage_frames`;
+    rows / aux / k2 / k3: the outputs of `decode_detections` or `nms_detections` (k3 is not drawn; k2 is needed with `keypoints`);
+    image_table (B, 16): the decode's; gt: None, or (dimensions (B, M, 3), locations (B, M, 3), rotys (B, M), reg_mask (B, M)) of the
+    targets; in_h, in_w: the padded input size (or a `canvas` of the right shape); without them it is read from the image table's
+    first row, which waits for the device.
+    table (with `want_table`): (entries (B, S, 12) int32, counts (B,) int32, float ends (B, S, 4)).  No host synchronisation."""
+    staged = _staged(frames)
+    _lib.require_cuda(staged, rows, aux, image_table)
+    K = int(K)
+    rows, aux, image_table = _f32c(rows).reshape(-1, 14), _f32c(aux).reshape(-1, 4), _f32c(image_table)
+    n = rows.shape[0]
+    if K < 1 or n % K or aux.shape[0] != n:
+        raise ValueError("rows %s and aux %s do not hold blocks of K = %d" % (tuple(rows.shape), tuple(aux.shape), K))
+    B = n // K
+    if tuple(image_table.shape) != (B, 16):
+        raise ValueError("image table %s for %d images" % (tuple(image_table.shape), B))
+    nk = 0
+    if keypoints:
+        if k2 is None:
+            raise ValueError("render_detections(keypoints=True) needs the decode's key points (records=True)")
+        k2 = _f32c(k2)
+        nk = k2.shape[1]
+        if tuple(k2.shape) != (n, nk, 2):
+            raise ValueError("key points %s for %d rows" % (tuple(k2.shape), n))
+    M, g = 0, [None] * 4
+    if gt is not None:
+        dims, locs, rotys, mask = gt
+        M = dims.shape[1]
+        g = [_f32c(dims), _f32c(locs), _f32c(rotys), mask.to(torch.uint8).contiguous()]
+        if tuple(g[0].shape) != (B, M, 3) or tuple(g[1].shape) != (B, M, 3) or tuple(g[2].shape) != (B, M) or tuple(g[3].shape) != (B, M):
+            raise ValueError("ground truth tables %s for %d images" % ([tuple(t.shape) for t in g], B))
+        _lib.require_cuda(*g)
+    if canvas is not None:
+        in_h, in_w = canvas.shape[1], canvas.shape[2] - canvas.shape[1]
+    if in_h is None or in_w is None:                         # the table's padded size: one read-back, which the passes avoid by naming it
+        in_w, in_h = (int(v) for v in image_table[0, 2:4].tolist())
+    in_h, in_w = int(in_h), int(in_w)
+    L = _lib.lib()
+    S = L.dcd_render_slots(M, K, nk)
+    if S < 1:
+        _lib.check(1, "dcd_render_detections (%d ground-truth slots, %d candidates, %d key points: over 8192 primitives)" % (M, K, nk))
+    dev = rows.device
+    if canvas is None:
+        canvas = torch.empty((B, in_h, in_w + in_h, 3), dtype=torch.uint8, device=dev)
+    elif tuple(canvas.shape) != (B, in_h, in_w + in_h, 3) or canvas.dtype != torch.uint8 or not canvas.is_contiguous():
+        raise ValueError("canvas %s %s" % (canvas.dtype, tuple(canvas.shape)))
+    entries = torch.empty((B, S, RENDER_ENTRY), dtype=torch.int32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    ends = torch.empty((B, S, 4), dtype=torch.float32, device=dev) if want_table else None
+    st = L.dcd_render_detections(_lib.stream_of(rows), staged.data_ptr(), staged.numel(), rows.data_ptr(), aux.data_ptr(), _lib.ptr(k2 if nk else None),
+                                 image_table.data_ptr(), _lib.ptr(g[0]), _lib.ptr(g[1]), _lib.ptr(g[2]), _lib.ptr(g[3]), B, K, nk, M,
+                                 in_h, in_w, float(det_threshold), float(vis_threshold), entries.data_ptr(), counts.data_ptr(),
+                                 _lib.ptr(ends), canvas.data_ptr())
+    _lib.check(st, "dcd_render_detections")
+    return canvas, ((entries, counts, ends) if want_table else None)
+
+
+def render_primitives(frames, table, counts, in_h, in_w, canvas=None):
+    """The renderer's second launch alone: a caller's primitive table (B, stride, 12) int32 and counts (B,) int32 drawn over the
+    staged frames -> canvas (B, in_h, in_w + in_h, 3) uint8.  Entries that are no valid primitive are passed over
+    (include/dcd_hip.h); the greatest `order` wins a pixel, then the later entry."""
+    staged = _staged(frames)
+    _lib.require_cuda(staged, table, counts)
+    if table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != RENDER_ENTRY or not table.is_contiguous():
+        raise ValueError("table: contiguous int32 (B, stride, %d), got %s %s" % (RENDER_ENTRY, table.dtype, tuple(table.shape)))
+    B, stride = table.shape[0], table.shape[1]
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or not counts.is_contiguous():
+        raise ValueError("counts: contiguous int32 (%d,), got %s %s" % (B, counts.dtype, tuple(counts.shape)))
+    in_h, in_w = int(in_h), int(in_w)
+    if canvas is None:
+        canvas = torch.empty((B, in_h, in_w + in_h, 3), dtype=torch.uint8, device=table.device)
+    elif tuple(canvas.shape) != (B, in_h, in_w + in_h, 3) or canvas.dtype != torch.uint8 or not canvas.is_contiguous():
+        raise ValueError("canvas %s %s" % (canvas.dtype, tuple(canvas.shape)))
+    st = _lib.lib().dcd_render_primitives(_lib.stream_of(table), staged.data_ptr(), staged.numel(), table.data_ptr(), counts.data_ptr(),
+                                          B, stride, in_h, in_w, canvas.data_ptr())
+    _lib.check(st, "dcd_render_primitives")
+    return canvas

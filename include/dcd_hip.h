@@ -1002,6 +1002,39 @@ int dcd_nms_detections(void *stream, const float *rows, const float *aux, const 
                        int nk, int mode, double thresh, double det_threshold, int class_agnostic, float *rows_out, float *aux_out,
                        float *kpts2d_out, float *kpts3d_out, float *overlaps_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * The detections of a batch drawn on the device (csrc/render.hip; the raster rule is the header of csrc/render_math.h and
+ * DESIGN.md 6d): per image the frame with the 2-D boxes, projected 3-D boxes, key points and labels, and beside it a square
+ * bird's-eye panel, ground truth under detections, rank 0 on top.  Two launches: the primitive table, then the tiles.
+ *   staged      the input pipeline's staged buffer (dcd_preprocess_images): (B, 5) int64 records -- byte offset, row pitch,
+ *               height, width, flip -- then the packed uint8 RGB frames; 8-byte aligned, staged_bytes long.  A record that does
+ *               not describe a frame inside the buffer and the canvas gives an all-zero picture, never a read outside.
+ *               A set flip flag mirrors the frame, as the preprocessing did for the model.
+ *   rows (B K, 14), aux (B K, 4), kpts2d (B K, nk, 2) or NULL with nk = 0: dcd_decode_detections' / dcd_nms_detections' outputs.
+ *               A row is drawn iff aux[., 0] >= det_threshold and rows[., 13] > vis_threshold, both compared in float32.
+ *   image_table (B, 16): the decode's; only P is read.
+ *   gt_dims (B, M, 3) (l, h, w), gt_locs (B, M, 3) centres, gt_rotys (B, M), gt_mask (B, M) uint8: the targets' tables; all
+ *               NULL with M = 0 for a split without labels.
+ *   table (B, S, 12) int32, S = dcd_render_slots(M, K, nk); counts (B) int32; ends (B, S, 4) fp32 or NULL: outputs.  Entry =
+ *               panel, kind (-1 none, 0 segment, 1 glyph), x0, y0, x1, y1, thickness, r, g, b, order, glyph; counts[b] = one past
+ *               the last drawn entry; ends = the coordinates before truncation.  16-byte aligned table.
+ *   canvas (B, in_h, in_w + in_h, 3) uint8, 4-byte aligned: every byte is written.
+ * dcd_render_primitives is the second launch alone on a caller's table (B, stride, 12) and counts; an entry that is not a valid
+ * primitive (unknown kind or panel, a coordinate of magnitude >= 2^24, thickness outside 1 .. 4, order outside [0, 2^18), glyph
+ * outside 0 .. 14) is passed over, and counts are clamped to [0, stride].
+ * No global atomics and no dependence on scheduling: two calls give the same bytes.
+ * dcd_render_slots: S, or -1 when M, K (1 .. 128), nk (0 .. 128) are out of range or S exceeds 8192 entries.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for such a configuration, a null or misaligned pointer, B outside 1 .. 65535,
+ * in_h / in_w outside 1 .. 16384, staged_bytes < 40 B, stride outside 1 .. 8192 or a NaN threshold.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_render_slots(int M, int K, int nk);
+int dcd_render_detections(void *stream, const uint8_t *staged, size_t staged_bytes, const float *rows, const float *aux,
+                          const float *kpts2d, const float *image_table, const float *gt_dims, const float *gt_locs,
+                          const float *gt_rotys, const uint8_t *gt_mask, int B, int K, int nk, int M, int in_h, int in_w,
+                          double det_threshold, double vis_threshold, int *table, int *counts, float *ends, uint8_t *canvas);
+int dcd_render_primitives(void *stream, const uint8_t *staged, size_t staged_bytes, const int *table, const int *counts, int B,
+                          int stride, int in_h, int in_w, uint8_t *canvas);
+
 #ifdef __cplusplus
 }
 #endif
