@@ -103,11 +103,9 @@ class _DCNWithOffsets(Function):
     def forward(ctx, input, w_off, b_off, weight, bias, geometry):
         from dcd_amd import ops
         input, w_off, weight = input.contiguous(), w_off.contiguous(), weight.contiguous()
-        ctx.cprec = ops._conv_prec(input)                      # the backward runs outside the forward's precision scope
-        p = _precision_scope()
+        p = _precision_scope()                                 # the backward runs outside the forward's precision scope
         ctx.precision = {} if p == "f32" else {"precision": p}
-        tw, ctx.tw_back = (ops.conv3x3_step_weights(w_off, input) if ops._PREP_BOTH and ctx.needs_input_grad[0] else (None, None))
-        out = ops._conv3x3_call(input, w_off, w_off.shape[0], False, b_off.contiguous(), transformed=tw, prec=ctx.cprec)
+        out = ops._conv3x3_forward(ctx, input, w_off, b_off.contiguous())      # leaves ctx.prec and ctx.tw_back
         offset, mask = _offset_mask_split(out)
         ctx.geometry = geometry
         ctx.save_for_backward(input, offset, mask, weight, bias, w_off)
@@ -123,8 +121,8 @@ class _DCNWithOffsets(Function):
         gout = _offset_mask_merge(grad_offset, grad_mask, mask)
         if ctx.needs_input_grad[0]:
             grad_input = ops._conv3x3_call(gout, w_off, w_off.shape[1], True, residual=grad_input.contiguous(), transformed=ctx.tw_back,
-                                           prec=ctx.cprec)
-        gw_off = ops._conv3x3_wrw_call(input, gout, w_off.shape, ctx.cprec) if ctx.needs_input_grad[1] else None
+                                           prec=ctx.prec)
+        gw_off = ops._conv3x3_wrw_call(input, gout, w_off.shape, ctx.prec) if ctx.needs_input_grad[1] else None
         gb_off = ops.channel_sums(gout) if ctx.needs_input_grad[2] else None
         return grad_input, gw_off, gb_off, grad_weight, grad_bias, None
 
@@ -211,9 +209,7 @@ class DCN(DCNv2):
         from dcd_amd import ops
         com = self.conv_offset_mask
         if (_ONE_NODE and _FUSED_GLUE and input.dtype == torch.float32 and not torch.is_autocast_enabled(input.device.type)
-                and com.bias is not None and com.groups == 1 and com.padding_mode == "zeros" and not isinstance(com.padding, str)
-                and ops.conv3x3_bias_supported(input, com.weight, com.stride, com.padding, com.dilation)
-                and ops._WRW_ENABLED and ops._OFFSET_CONV_FWD):
+                and ops.offset_conv_in_dcn_node(input, com)):
             geometry = (*self.kernel_size, *self.stride, *self.padding, *self.dilation, int(self.deformable_groups))
             return _DCNWithOffsets.apply(input, com.weight, com.bias, self.weight, self.bias, geometry)
         out = com(input)

@@ -17,46 +17,58 @@ _SKIP = os.environ.get("DCD_CONV_SKIP_NODE", "1") != "0"     # 0: conv + identit
 _STEM = os.environ.get("DCD_CONV_STEM", "1") != "0"          # 0: the two stem convolutions stay on the stock op (A/B timing)
 
 
+ROUTES = ("conv3x3", "conv3x3_with_skip", "conv3x3_stock_forward", "conv3x3_stride2_native", "conv3x3_stride2", "conv_stem",
+          "conv2d_bias", "stock")
+
+
+def conv2d_route(module, x, skip=False):
+    """Which entry point of `ops` runs `module` (an nn.Conv2d) on `x`: one of ROUTES, "stock" being `nn.Conv2d.forward`.
+    skip: the caller also wants x back for a skip connection (`forward_with_skip`), which "conv3x3_with_skip" serves."""
+    if not _ENABLED or module.groups != 1 or module.padding_mode != "zeros":
+        return "stock"
+    w, bias = module.weight, module.bias
+    if bias is None and module.kernel_size == (3, 3) and module.padding == (1, 1) and module.dilation == (1, 1):
+        if module.stride == (1, 1):
+            if ops.conv3x3_supported(x, w):
+                return "conv3x3_with_skip" if skip and _SKIP and torch.is_grad_enabled() and x.requires_grad else "conv3x3"
+            if torch.is_grad_enabled() and w.requires_grad and ops.conv3x3_wrw_only_supported(x, w):
+                return "conv3x3_stock_forward"
+        elif module.stride == (2, 2):
+            if ops.conv3x3_stride2_native_supported(x, w):
+                return "conv3x3_stride2_native"                            # exact fp32: csrc/conv_s2_f32.inc
+            if ops.conv3x3_stride2_supported(x, w):
+                return "conv3x3_stride2"
+    if isinstance(module.padding, str):
+        return "stock"
+    if bias is None:
+        if (_STEM and ops.conv_stem_supported(x, w, module.stride, module.padding, module.dilation, module.groups)
+                and (w.shape[1] == 16 or not x.requires_grad)):
+            return "conv_stem"
+    # a biased layer: its bias gradient on csrc/norm.hip once the map is large; a 3x3 one entirely on csrc/conv.hip
+    elif (x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and bias.requires_grad
+            and (x.shape[0] * x.shape[2] * x.shape[3] >= 1 << 16
+                 or ops.conv3x3_bias_supported(x, w, module.stride, module.padding, module.dilation))):
+        return "conv2d_bias"
+    return "stock"
+
+
 class Conv2d(nn.Conv2d):
     def forward(self, x):
-        if (_ENABLED and self.bias is None and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros"
-                and ops.conv3x3_supported(x, self.weight)):
-            return ops.conv3x3(x, self.weight)
-        if (_ENABLED and self.bias is None and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros" and torch.is_grad_enabled()
-                and self.weight.requires_grad and ops.conv3x3_wrw_only_supported(x, self.weight)):
-            return ops.conv3x3_stock_forward(x, self.weight)
-        if (_ENABLED and self.bias is None and self.kernel_size == (3, 3) and self.stride == (2, 2) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros"
-                and ops.conv3x3_stride2_native_supported(x, self.weight)):
-            return ops.conv3x3_stride2_native(x, self.weight)              # exact fp32: csrc/conv_s2_f32.inc (round 6)
-        if (_ENABLED and self.bias is None and self.kernel_size == (3, 3) and self.stride == (2, 2) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros"
-                and ops.conv3x3_stride2_supported(x, self.weight)):
-            return ops.conv3x3_stride2(x, self.weight)
-        if (_ENABLED and _STEM and self.bias is None and self.padding_mode == "zeros" and not isinstance(self.padding, str)
-                and ops.conv_stem_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups)
-                and (self.weight.shape[1] == 16 or not x.requires_grad)):
-            return ops.conv_stem(x, self.weight)
-        if (_ENABLED and self.bias is not None and x.is_cuda and x.dtype == torch.float32 and self.groups == 1
-                and self.padding_mode == "zeros" and not isinstance(self.padding, str) and torch.is_grad_enabled()
-                and self.bias.requires_grad
-                and (x.shape[0] * x.shape[2] * x.shape[3] >= 1 << 16
-                     or ops.conv3x3_bias_supported(x, self.weight, self.stride, self.padding, self.dilation))):
-            return ops.conv2d_bias(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
-        ops.stock_conv_in_capture(self, x)                  # raises for a stride-2 3x3 layer inside a stream capture
-        return super().forward(x)
+        return self._run(conv2d_route(self, x), x)
 
+    def _run(self, route, x):
+        if route == "stock":
+            ops.stock_conv_in_capture(self, x)              # raises for a stride-2 3x3 layer inside a stream capture
+            return super().forward(x)
+        if route == "conv2d_bias":
+            return ops.conv2d_bias(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
+        return getattr(ops, route)(x, self.weight)
 
     def forward_with_skip(self, x):
         """(self(x), x): for a block whose skip connection starts at this convolution's input.  On the Winograd path the skip's
         gradient is added inside the input-gradient kernel (ops.conv3x3_with_skip); otherwise x itself is returned."""
-        if (_ENABLED and _SKIP and self.bias is None and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
-                and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros" and torch.is_grad_enabled()
-                and x.requires_grad and ops.conv3x3_supported(x, self.weight)):
-            return ops.conv3x3_with_skip(x, self.weight)
-        return self.forward(x), x
+        route = conv2d_route(self, x, skip=True)
+        return self._run(route, x) if route == "conv3x3_with_skip" else (self._run(route, x), x)
 
 
 class DepthwiseUpsample(nn.ConvTranspose2d):
@@ -79,12 +91,8 @@ class DepthwiseUpsample(nn.ConvTranspose2d):
                 and self.dilation == (1, 1) and (x.shape[3] * f) % 4 == 0 and x.shape[0] * x.shape[1] <= 65535)
 
     def forward(self, x, output_size=None):
-        f = self.stride[0]
-        if (_ENABLED and output_size is None and x.is_cuda and x.dtype == torch.float32 and self.bias is None
-                and self.groups == self.in_channels == self.out_channels and self.stride == (f, f) and f in (2, 4, 8)
-                and self.kernel_size == (2 * f, 2 * f) and self.padding == (f // 2, f // 2) and self.output_padding == (0, 0)
-                and self.dilation == (1, 1) and (x.shape[3] * f) % 4 == 0 and x.shape[0] * x.shape[1] <= 65535):
-            return ops.upsample_dw(x, self.weight, f)
+        if self._hip_ok(x, output_size):
+            return ops.upsample_dw(x, self.weight, self.stride[0])
         return super().forward(x, output_size)
 
 

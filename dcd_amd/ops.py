@@ -890,13 +890,21 @@ def batch_norm_act_eval(x, residual, weight, bias, running_mean, running_var, ep
 _CONV_MIN_MAP = int(os.environ.get("DCD_CONV_MIN_MAP", str(12 * 40)))      # A/B timing: 7680 restores the round-1 dispatch
 
 
+def _device_f32_kxk(x, weight, k=3):
+    """A device fp32 input and a 4-D k x k weight: what every convolution kernel of this file asks first."""
+    return x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2] == k and weight.shape[3] == k
+
+
+def _winograd_map(H, W, cin, least=None):
+    """The stride-1 Winograd kernels' map rule; least: the smallest map in pixels (default: _CONV_MIN_MAP at call time)."""
+    return W % 4 == 0 and H % 2 == 0 and cin >= 64 and H * W >= (_CONV_MIN_MAP if least is None else least)
+
+
 def conv3x3_supported(x, weight):
     """Shapes the HIP kernel is used for: 3x3 weight, W % 4 == 0, H even, at least 64 input and output channels (narrower
     layers would idle most of a 64-wide output slice), maps of at least 12x40 (the 12 x 20 px regions and the split
     contraction of csrc/conv.hip keep every CU busy there; tools/time_conv.py)."""
-    return (x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2] == 3 and weight.shape[3] == 3
-            and x.shape[3] % 4 == 0 and x.shape[2] % 2 == 0 and weight.shape[0] >= 64 and weight.shape[1] >= 64
-            and x.shape[2] * x.shape[3] >= _CONV_MIN_MAP)
+    return _device_f32_kxk(x, weight) and weight.shape[0] >= 64 and _winograd_map(x.shape[2], x.shape[3], weight.shape[1])
 
 
 _CONV_SPLIT_MIN_MAP = int(os.environ.get("DCD_CONV_SPLIT_MIN_MAP", "7680"))
@@ -922,10 +930,6 @@ def _conv_prec(like=None):
     return PREC_BF16 if hw is None or hw >= _CONV_BF16_MIN_MAP else PREC_F32
 
 
-def _conv_split(like=None):
-    return _conv_prec(like) != PREC_F32
-
-
 def _wrw_prec(prec):
     """The weight-gradient kernel has the exact and the one-product form (no split one)."""
     return PREC_BF16 if prec == PREC_BF16 else PREC_F32
@@ -934,6 +938,8 @@ def _wrw_prec(prec):
 class SplitWeights:
     """Winograd-domain weights in split-bf16 layout (dcd_conv3x3_split_transform_weights); a marker type so that the call knows
     which kernel they belong to, and with which precision (DCD_PREC_BF16X3 / DCD_PREC_BF16: the same layout) it runs."""
+
+    layout_key = True                                  # its row in `_LAYOUTS`
 
     def __init__(self, tensor, prec):
         self.tensor = tensor
@@ -944,8 +950,10 @@ class Bf16Weights(SplitWeights):
     """bf16-rounded weights in the operand order of the direct one-product kernel (dcd_conv3x3_bf16_transform_weights,
     csrc/conv_direct_bf16.inc): what DCD_PREC_BF16 runs on unless DCD_CONV_BF16_DIRECT=0 keeps the Winograd form (A/B timing)."""
 
-    def __init__(self, tensor):
-        super().__init__(tensor, PREC_BF16)
+    layout_key = "bf16"
+
+    def __init__(self, tensor, prec=PREC_BF16):
+        super().__init__(tensor, prec)
 
 
 _BF16_DIRECT = os.environ.get("DCD_CONV_BF16_DIRECT", "1") != "0"
@@ -958,6 +966,28 @@ def _layout(prec):
     return "bf16" if prec == PREC_BF16 and _BF16_DIRECT else "split"
 
 
+class _Layout:
+    """One prepared-weight layout: the names of its library entry points, the dtype of its buffers and the marker type its
+    buffers travel in (None: the bare tensor)."""
+
+    def __init__(self, stem, dtype, wrapper):
+        self.weights_bytes, self.workspace_bytes, self.prepared = stem + "_weights_bytes", stem + "_workspace_bytes", stem + "_prepared"
+        self.transform, self.table = stem + "_transform_weights", stem + "_transform_weights_table"
+        self.dtype, self.wrapper = dtype, wrapper
+
+    def buffer(self, L, Ci, Co, backward_data, device):
+        return torch.empty(getattr(L, self.weights_bytes)(Ci, Co, backward_data) // 4, dtype=self.dtype, device=device)
+
+    def wrap(self, tensor, prec):
+        return tensor if tensor is None or self.wrapper is None else self.wrapper(tensor, prec)
+
+
+# by the layout part of `_PREPARED`'s keys: False fp32 Winograd, True split-bf16 (hi | lo) Winograd, "bf16" the direct kernel's
+_LAYOUTS = {False: _Layout("dcd_conv3x3", torch.float32, None), True: _Layout("dcd_conv3x3_split", torch.int32, SplitWeights),
+            "bf16": _Layout("dcd_conv3x3_bf16", torch.int32, Bf16Weights)}
+_LAYOUT_KEY = {"f32": False, "split": True, "bf16": "bf16"}      # `_layout`'s names
+
+
 def conv3x3_transform_weights(weight, forward=True, backward=True, like=None, prec=None):
     """Winograd-domain weights of a (Cout, Cin, 3, 3) filter for the forward and / or the backward-data call, ONE launch
     (split-bf16 form: one launch per direction).  like: the tensor the convolution will run on (decides the form, see _conv_prec);
@@ -965,23 +995,11 @@ def conv3x3_transform_weights(weight, forward=True, backward=True, like=None, pr
     L = _lib.lib()
     Co, Ci = weight.shape[0], weight.shape[1]
     prec = _conv_prec(like) if prec is None else prec
-    if _layout(prec) == "bf16":
-        tf = torch.empty(L.dcd_conv3x3_bf16_weights_bytes(Ci, Co, 0) // 4, dtype=torch.int32, device=weight.device) if forward else None
-        tb = torch.empty(L.dcd_conv3x3_bf16_weights_bytes(Ci, Co, 1) // 4, dtype=torch.int32, device=weight.device) if backward else None
-        _lib.check(L.dcd_conv3x3_bf16_transform_weights(_lib.stream_of(weight), weight.data_ptr(), Ci, Co, _lib.ptr(tf), _lib.ptr(tb)),
-                   "dcd_conv3x3_bf16_transform_weights")
-        return (Bf16Weights(tf) if forward else None), (Bf16Weights(tb) if backward else None)
-    if prec != PREC_F32:
-        tf = torch.empty(L.dcd_conv3x3_split_weights_bytes(Ci, Co, 0) // 4, dtype=torch.int32, device=weight.device) if forward else None
-        tb = torch.empty(L.dcd_conv3x3_split_weights_bytes(Ci, Co, 1) // 4, dtype=torch.int32, device=weight.device) if backward else None
-        _lib.check(L.dcd_conv3x3_split_transform_weights(_lib.stream_of(weight), weight.data_ptr(), Ci, Co, _lib.ptr(tf), _lib.ptr(tb)),
-                   "dcd_conv3x3_split_transform_weights")
-        return (SplitWeights(tf, prec) if forward else None), (SplitWeights(tb, prec) if backward else None)
-    tf = torch.empty(L.dcd_conv3x3_weights_bytes(Ci, Co, 0) // 4, dtype=torch.float32, device=weight.device) if forward else None
-    tb = torch.empty(L.dcd_conv3x3_weights_bytes(Ci, Co, 1) // 4, dtype=torch.float32, device=weight.device) if backward else None
-    _lib.check(L.dcd_conv3x3_transform_weights(_lib.stream_of(weight), weight.data_ptr(), Ci, Co, _lib.ptr(tf), _lib.ptr(tb)),
-               "dcd_conv3x3_transform_weights")
-    return tf, tb
+    lay = _LAYOUTS[_LAYOUT_KEY[_layout(prec)]]
+    tf = lay.buffer(L, Ci, Co, 0, weight.device) if forward else None
+    tb = lay.buffer(L, Ci, Co, 1, weight.device) if backward else None
+    _lib.check(getattr(L, lay.transform)(_lib.stream_of(weight), weight.data_ptr(), Ci, Co, _lib.ptr(tf), _lib.ptr(tb)), lay.transform)
+    return lay.wrap(tf, prec), lay.wrap(tb, prec)
 
 
 def _conv3x3_call(inp, weight, out_channels, backward_data, bias=None, residual=None, transformed=None, residual_inplace=True,
@@ -1004,34 +1022,24 @@ def _conv3x3_call(inp, weight, out_channels, backward_data, bias=None, residual=
         prec = _conv_prec(inp) if prec is None else prec
         if prec != PREC_F32:
             transformed = conv3x3_transform_weights(weight, not backward_data, backward_data, prec=prec)[1 if backward_data else 0]
-    if isinstance(transformed, Bf16Weights):
-        n = L.dcd_conv3x3_bf16_workspace_bytes(B, Ci, H, W, Co)
-        ws = torch.empty(max(n, 16), dtype=torch.uint8, device=inp.device)
-        st = L.dcd_conv3x3_bf16_prepared(_lib.stream_of(inp), inp.data_ptr(), transformed.tensor.data_ptr(), _lib.ptr(bias),
-                                         _lib.ptr(residual), out.data_ptr(), B, Ci, H, W, Co, 1 if backward_data else 0, ws.data_ptr(), n)
-        _lib.check(st, "dcd_conv3x3_bf16_prepared")
+    if transformed is None:                            # exact fp32: the call transforms its own weights into the workspace
+        n = L.dcd_conv3x3_workspace_bytes(B, Ci, H, W, Co)
+        ws = torch.empty(n, dtype=torch.uint8, device=inp.device)
+        st = L.dcd_conv3x3(_lib.stream_of(inp), inp.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), out.data_ptr(),
+                           B, Ci, H, W, Co, 1 if backward_data else 0, ws.data_ptr(), n)
+        _lib.check(st, "dcd_conv3x3")
         return out
-    if isinstance(transformed, SplitWeights):
-        n = L.dcd_conv3x3_split_workspace_bytes(B, Ci, H, W, Co)
-        ws = torch.empty(max(n, 16), dtype=torch.uint8, device=inp.device)
-        st = L.dcd_conv3x3_split_prepared(_lib.stream_of(inp), inp.data_ptr(), transformed.tensor.data_ptr(), _lib.ptr(bias),
-                                          _lib.ptr(residual), out.data_ptr(), B, Ci, H, W, Co, 1 if backward_data else 0,
-                                          transformed.prec, ws.data_ptr(), n)
-        _lib.check(st, "dcd_conv3x3_split_prepared")
-        return out
-    n = L.dcd_conv3x3_workspace_bytes(B, Ci, H, W, Co)
-    if transformed is not None:
+    key = getattr(transformed, "layout_key", False)    # a bare tensor: the fp32 layout
+    lay = _LAYOUTS[key]
+    n = getattr(L, lay.workspace_bytes)(B, Ci, H, W, Co)
+    if key is False:
         n = max(n - min(L.dcd_conv3x3_weights_bytes(Ci, Co, 0), L.dcd_conv3x3_weights_bytes(Ci, Co, 1)), 0)   # partial images only (upper bound)
-        ws = torch.empty(max(n, 16), dtype=torch.uint8, device=inp.device)
-        st = L.dcd_conv3x3_prepared(_lib.stream_of(inp), inp.data_ptr(), transformed.data_ptr(), _lib.ptr(bias), _lib.ptr(residual),
-                                    out.data_ptr(), B, Ci, H, W, Co, 1 if backward_data else 0, ws.data_ptr(), n)
-        _lib.check(st, "dcd_conv3x3_prepared")
-        return out
-    ws = torch.empty(n, dtype=torch.uint8, device=inp.device)
-    st = L.dcd_conv3x3(_lib.stream_of(inp), inp.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), out.data_ptr(),
-                       B, Ci, H, W, Co,
-                       1 if backward_data else 0, ws.data_ptr(), n)
-    _lib.check(st, "dcd_conv3x3")
+    ws = torch.empty(max(n, 16), dtype=torch.uint8, device=inp.device)
+    tw = transformed if key is False else transformed.tensor
+    prec_arg = (transformed.prec,) if key is True else ()          # the split kernel runs DCD_PREC_BF16X3 and DCD_PREC_BF16
+    st = getattr(L, lay.prepared)(_lib.stream_of(inp), inp.data_ptr(), tw.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), out.data_ptr(),
+                                  B, Ci, H, W, Co, 1 if backward_data else 0, *prec_arg, ws.data_ptr(), n)
+    _lib.check(st, lay.prepared)
     return out
 
 
@@ -1089,17 +1097,9 @@ class _PreparedWeights:
         e = self.entries.get(id(weight))
         if e is not None and e[0]() is weight and e[1] == weight.data_ptr():
             return
-        L = _lib.lib()
+        L, lay = _lib.lib(), _LAYOUTS[self.split]
         Co, Ci = weight.shape[0], weight.shape[1]
-        if self.split == "bf16":
-            tf = torch.empty(L.dcd_conv3x3_bf16_weights_bytes(Ci, Co, 0) // 4, dtype=torch.int32, device=weight.device)
-            tb = torch.empty(L.dcd_conv3x3_bf16_weights_bytes(Ci, Co, 1) // 4, dtype=torch.int32, device=weight.device)
-        elif self.split:
-            tf = torch.empty(L.dcd_conv3x3_split_weights_bytes(Ci, Co, 0) // 4, dtype=torch.int32, device=weight.device)
-            tb = torch.empty(L.dcd_conv3x3_split_weights_bytes(Ci, Co, 1) // 4, dtype=torch.int32, device=weight.device)
-        else:
-            tf = torch.empty(L.dcd_conv3x3_weights_bytes(Ci, Co, 0) // 4, dtype=torch.float32, device=weight.device)
-            tb = torch.empty(L.dcd_conv3x3_weights_bytes(Ci, Co, 1) // 4, dtype=torch.float32, device=weight.device)
+        tf, tb = lay.buffer(L, Ci, Co, 0, weight.device), lay.buffer(L, Ci, Co, 1, weight.device)
         self.entries[id(weight)] = [weakref.ref(weight), weight.data_ptr(), tf, tb, -1, 0]
         self.dirty = True
         _watch_optimizer_steps()
@@ -1132,17 +1132,14 @@ class _PreparedWeights:
                 self._immortal.append(self.table)      # a live graph may still launch the transform on the old table
             self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
             self.dirty = False
-        L = _lib.lib()
-        fn = (L.dcd_conv3x3_bf16_transform_weights_table if self.split == "bf16" else
-              L.dcd_conv3x3_split_transform_weights_table if self.split else L.dcd_conv3x3_transform_weights_table)
-        _lib.check(fn(_lib.stream_of(self.table), self.table.data_ptr(), len(self.order)), "dcd_conv3x3_transform_weights_table")
+        name = _LAYOUTS[self.split].table
+        _lib.check(getattr(_lib.lib(), name)(_lib.stream_of(self.table), self.table.data_ptr(), len(self.order)), name)
         for e in self.order:
             e[4] = e[0]()._version
             e[5] += 1
 
 
-_PREPARED = {}                     # (device index, layout: False fp32 | True split | "bf16" direct) -> _PreparedWeights
-_LAYOUT_KEYS = (False, True, "bf16")
+_PREPARED = {}                     # (device index, layout: a key of _LAYOUTS) -> _PreparedWeights
 
 
 _STEP_HOOK = None
@@ -1164,17 +1161,20 @@ def _watch_optimizer_steps():
         _STEP_HOOK = register_optimizer_step_post_hook(_invalidate_all_conv_weights)
 
 
+def _prepared_on(device):
+    """The weight tables of `device` (default: the current one), in the order of `_LAYOUTS`."""
+    if not torch.cuda.is_available():
+        return []
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    return [_PREPARED[idx, key] for key in _LAYOUTS if (idx, key) in _PREPARED]
+
+
 def invalidate_conv_weights(device=None):
     """Forget that the table's entries are current (the next `refresh_conv_weights` re-validates them).  For code that changes
     parameters without going through autograd's version counters -- a replayed HIP graph that contains the optimizer step."""
-    if not torch.cuda.is_available():
-        return
-    idx = torch.cuda.current_device() if device is None else torch.device(device).index
-    for split in _LAYOUT_KEYS:
-        p = _PREPARED.get((idx, split))
-        if p is not None:
-            for e in p.entries.values():
-                e[4] = -1
+    for p in _prepared_on(device):
+        for e in p.entries.values():
+            e[4] = -1
 
 
 def conv3x3_step_weights(weight, like):
@@ -1182,16 +1182,14 @@ def conv3x3_step_weights(weight, like):
     current (no launch), else transformed now -- both directions, one launch -- and the layer is registered for the next
     `refresh_conv_weights`."""
     prec = _conv_prec(like)
-    split = {"f32": False, "split": True, "bf16": "bf16"}[_layout(prec)]
+    split = _LAYOUT_KEY[_layout(prec)]
     key = (like.device.index, split)
     prepared = _PREPARED.get(key)
     if prepared is None:
         prepared = _PREPARED[key] = _PreparedWeights(split)
     e = prepared.lookup(weight)
     if e is not None:
-        if split == "bf16":
-            return Bf16Weights(e[2]), Bf16Weights(e[3])
-        return (SplitWeights(e[2], prec), SplitWeights(e[3], prec)) if split else (e[2], e[3])
+        return _LAYOUTS[split].wrap(e[2], prec), _LAYOUTS[split].wrap(e[3], prec)
     prepared.register(weight)
     return conv3x3_transform_weights(weight, prec=prec)
 
@@ -1200,13 +1198,8 @@ def refresh_conv_weights(device=None):
     """Transform the weights of every registered 3x3 convolution on `device` (default: the current one) in one launch, on the
     current stream.  Call it after the optimizer step / before the forward of a train step; calling it never is allowed (every
     convolution then transforms its own weights, as before)."""
-    if not torch.cuda.is_available():
-        return
-    idx = torch.cuda.current_device() if device is None else torch.device(device).index
-    for split in _LAYOUT_KEYS:
-        p = _PREPARED.get((idx, split))
-        if p is not None:
-            p.refresh()
+    for p in _prepared_on(device):
+        p.refresh()
 _WRW_ENABLED = os.environ.get("DCD_CONV_WRW", "1") != "0"        # 0: weight gradient on the stock op (A/B timing)
 
 
@@ -1224,6 +1217,37 @@ def _conv3x3_wrw_call(x, gy, wshape, prec=PREC_F32):
     return gw
 
 
+def _conv3x3_weight_grad(x, gy, weight, prec, conf=None):
+    """dL/dw of a layer whose forward ran on csrc/conv.hip: the own kernel, or the stock op under DCD_CONV_WRW=0.
+    conf: the layer's (stride, padding, dilation) as lists, for the stock op (default: 1, 1, 1)."""
+    if _WRW_ENABLED:
+        return _conv3x3_wrw_call(x, gy, weight.shape, prec)
+    return torch.ops.aten.convolution_backward(gy, x, weight, None, *(conf or ([1, 1], [1, 1], [1, 1])), False, [0, 0], 1,
+                                               [False, True, False])[1]
+
+
+def _conv3x3_forward(ctx, x, weight, bias=None):
+    """conv2d(x, weight, bias, stride 1, padding 1) in a node's forward.  Leaves on ctx for its backward: `prec` (the backward runs
+    outside the forward's precision scope) and `tw_back`, the backward-data weights (they do not change in between)."""
+    ctx.prec = _conv_prec(x)
+    tw, ctx.tw_back = conv3x3_step_weights(weight, x) if _PREP_BOTH and ctx.needs_input_grad[0] else (None, None)
+    return _conv3x3_call(x, weight, weight.shape[0], False, bias, transformed=tw, prec=ctx.prec)
+
+
+def _conv3x3_backward(ctx, gy, gskip=None):
+    """(dL/dx, dL/dw) of `_Conv3x3` / `_Conv3x3Skip`; gskip: a gradient that arrives at x by another way, added inside the
+    input-gradient kernel (read only: the tensor belongs to autograd)."""
+    x, weight = ctx.saved_tensors
+    gy = _f32c(gy)
+    gx = gw = None
+    if ctx.needs_input_grad[0]:
+        gx = _conv3x3_call(gy, weight, weight.shape[1], True, residual=None if gskip is None else _f32c(gskip),
+                           transformed=ctx.tw_back, residual_inplace=False, prec=ctx.prec)
+    if ctx.needs_input_grad[1]:
+        gw = _conv3x3_weight_grad(x, gy, weight, ctx.prec)
+    return gx, gw
+
+
 class _Conv3x3(torch.autograd.Function):
     """y = conv2d(x, w, stride 1, padding 1), dL/dx and dL/dw on csrc/conv.hip (Winograd F(2x2,3x3) on the fp32 matrix
     pipe; MIOpen's implicit-GEMM weight gradient runs near the fp32 matrix peak but does 2.25x the multiplies and needs
@@ -1234,29 +1258,12 @@ class _Conv3x3(torch.autograd.Function):
         _lib.require_cuda(x, weight)
         x, weight = _f32c(x), _f32c(weight)
         ctx.save_for_backward(x, weight)
-        ctx.tw_back = None
-        ctx.prec = _conv_prec(x)                       # the backward runs outside the forward's precision scope
-        if _PREP_BOTH and ctx.needs_input_grad[0]:
-            # the weights of this call and of its backward-data call (they do not change in between)
-            tw, ctx.tw_back = conv3x3_step_weights(weight, x)
-            return _conv3x3_call(x, weight, weight.shape[0], False, transformed=tw)
-        return _conv3x3_call(x, weight, weight.shape[0], False, prec=ctx.prec)
+        return _conv3x3_forward(ctx, x, weight)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        gy = _f32c(gy)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = _conv3x3_call(gy, weight, weight.shape[1], True, transformed=ctx.tw_back, prec=ctx.prec)
-        if ctx.needs_input_grad[1]:
-            if _WRW_ENABLED:
-                gw = _conv3x3_wrw_call(x, gy, weight.shape, ctx.prec)
-            else:
-                gw = torch.ops.aten.convolution_backward(gy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [False, True, False])[1]
-        return gx, gw
+        return _conv3x3_backward(ctx, gy)
 
 
 def conv3x3(x, weight):
@@ -1274,26 +1281,14 @@ class _Conv3x3Skip(torch.autograd.Function):
         _lib.require_cuda(x, weight)
         x, weight = _f32c(x), _f32c(weight)
         ctx.save_for_backward(x, weight)
-        ctx.prec = _conv_prec(x)
-        tw, ctx.tw_back = conv3x3_step_weights(weight, x) if _PREP_BOTH and ctx.needs_input_grad[0] else (None, None)
-        return _conv3x3_call(x, weight, weight.shape[0], False, transformed=tw, prec=ctx.prec), x.view_as(x)
+        return _conv3x3_forward(ctx, x, weight), x.view_as(x)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy, gskip):
-        x, weight = ctx.saved_tensors
-        gx = gw = None
         if gy is None:                                      # only the skip was used
             return gskip, None
-        gy = _f32c(gy)
-        if ctx.needs_input_grad[0]:
-            res = None if gskip is None else _f32c(gskip)   # read only: the gradient tensor belongs to autograd
-            gx = _conv3x3_call(gy, weight, weight.shape[1], True, residual=res, transformed=ctx.tw_back, residual_inplace=False,
-                               prec=ctx.prec)
-        if ctx.needs_input_grad[1]:
-            gw = (_conv3x3_wrw_call(x, gy, weight.shape, ctx.prec) if _WRW_ENABLED else
-                  torch.ops.aten.convolution_backward(gy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1])
-        return gx, gw
+        return _conv3x3_backward(ctx, gy, gskip)
 
 
 def conv3x3_with_skip(x, weight):
@@ -1387,7 +1382,7 @@ class _S2DFilter(torch.autograd.Function):
 def conv3x3_stride2_supported(x, weight):
     """Stride-2 layers the space-to-depth form takes: even H, W % 8 == 0 (the half-resolution map must satisfy the stride-1 kernel's
     W % 4 == 0, H even -> H % 4 == 0), at least 64 channels after the regrouping (4 Cin) and a half-resolution map of 12 x 40."""
-    if _S2D_MODE == "0" or not (x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+    if _S2D_MODE == "0" or not _device_f32_kxk(x, weight):
         return False
     if _S2D_MODE != "1" and _conv_prec() == PREC_F32:
         return False                                   # exact fp32 keeps the stock solver (2.72 against 3.75 ms per bs-8 step) unless
@@ -1398,7 +1393,7 @@ def conv3x3_stride2_supported(x, weight):
         # size -- maps off the alignment rules are zero-padded (conv3x3_stride2), small ones are slow but never on the stock solver
         # inside a capture (DLA levels 4 / 5 at 96x320, inputs whose deep maps are below 24x80)
         return 4 * weight.shape[1] >= 64
-    return H % 4 == 0 and W % 8 == 0 and 4 * weight.shape[1] >= 64 and (H // 2) * (W // 2) >= _CONV_MIN_MAP
+    return H % 2 == 0 and W % 2 == 0 and _winograd_map(H // 2, W // 2, 4 * weight.shape[1])
 
 
 def conv3x3_stride2(x, weight):
@@ -1434,7 +1429,7 @@ def conv3x3_stride2_native_supported(x, weight):
     (profiles/r06_stride2.txt): forward 124 / 110 / 104 / 107 / 125 us against the stock solver's 221 / 174 / 150 / 131 / 128, input
     gradient 227 / 121 / 124 / 132 / 148 against 243 / 186 / 180 / 157 / 164, weight gradient 231 / 178 / 126 / 121 / 127 against
     368 / 203 / 125 / 122 / 116: 2.1 ms for the five layers where the stock solver takes 2.7 and the space-to-depth form 3.75."""
-    if not (_S2_NATIVE and x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+    if not (_S2_NATIVE and _device_f32_kxk(x, weight)):
         return False
     # inside the split-bf16 scope as well (a scope permits reduced products, it does not oblige them): the exact kernels take 2.1 ms
     # for the five layers where the split space-to-depth form takes 3.75 -- bf16x3 step 34.4 -> 33.2 ms.  Not inside the bf16 scope:
@@ -1493,9 +1488,8 @@ def conv3x3_stride2_native(x, weight):
 def conv3x3_wrw_only_supported(x, weight):
     """Maps below the forward kernel's limit (only when DCD_CONV_MIN_MAP raises it) where the weight-gradient kernel still
     wins (256->256 @ 24x80: 0.14 vs 0.18 ms incl. the stock path's transposes, tools/time_conv.py)."""
-    return (_WRW_ENABLED and x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2] == 3
-            and weight.shape[3] == 3 and x.shape[3] % 4 == 0 and x.shape[2] % 2 == 0 and weight.shape[0] >= 64
-            and weight.shape[1] >= 64 and 24 * 80 <= x.shape[2] * x.shape[3] < _CONV_MIN_MAP)
+    return (_WRW_ENABLED and _device_f32_kxk(x, weight) and weight.shape[0] >= 64
+            and _winograd_map(x.shape[2], x.shape[3], weight.shape[1], 24 * 80) and x.shape[2] * x.shape[3] < _CONV_MIN_MAP)
 
 
 class _Conv3x3StockFwd(torch.autograd.Function):
@@ -1530,7 +1524,7 @@ def conv3x3_stock_forward(x, weight):
 # ----------------------------------------------------------------------------------------------
 def conv_stem_supported(x, weight, stride, padding, dilation, groups):
     k = weight.shape[2]
-    return (x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and weight.shape[0] == 16 and weight.shape[2] == weight.shape[3]
+    return (_device_f32_kxk(x, weight, k) and weight.shape[0] == 16
             and (weight.shape[1], k) in ((16, 3), (3, 7)) and tuple(stride) == (1, 1) and tuple(padding) == (k // 2, k // 2)
             and tuple(dilation) == (1, 1) and groups == 1 and x.shape[3] % 4 == 0 and x.shape[2] * x.shape[3] >= 1 << 16)
 
@@ -1754,9 +1748,15 @@ def channel_sums(gy):
 
 def conv3x3_bias_supported(x, weight, stride, padding, dilation):
     """Biased 3x3 / stride 1 / pad 1 layers that run on csrc/conv.hip end to end (see _ConvBias)."""
-    return (_OFFSET_CONV_BWD and x.is_cuda and x.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2] == 3
-            and weight.shape[3] == 3 and (list(stride), list(padding), list(dilation)) == ([1, 1], [1, 1], [1, 1])
-            and x.shape[3] % 4 == 0 and x.shape[2] % 2 == 0 and weight.shape[1] >= 64 and x.shape[2] * x.shape[3] >= _CONV_MIN_MAP)
+    return (_OFFSET_CONV_BWD and _device_f32_kxk(x, weight) and (list(stride), list(padding), list(dilation)) == ([1, 1], [1, 1], [1, 1])
+            and _winograd_map(x.shape[2], x.shape[3], weight.shape[1]))
+
+
+def offset_conv_in_dcn_node(x, conv):
+    """Whether a DCN's offset convolution (`conv`: a biased layers.conv.Conv2d) can run inside the DCN's own autograd node
+    (`_DCNWithOffsets`): forward, input gradient and weight gradient all on csrc/conv.hip -- the node has no stock fallback."""
+    return (_WRW_ENABLED and _OFFSET_CONV_FWD and conv.bias is not None and conv.groups == 1 and conv.padding_mode == "zeros"
+            and not isinstance(conv.padding, str) and conv3x3_bias_supported(x, conv.weight, conv.stride, conv.padding, conv.dilation))
 
 
 class _ConvBias(torch.autograd.Function):
@@ -1784,21 +1784,16 @@ class _ConvBias(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
-        stride, padding, dilation = ctx.conf
         gy = _f32c(gy)
-        ours = ctx.ours
-        ours_w = ours and _WRW_ENABLED
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gx = gw = None
-        if ours and ctx.needs_input_grad[0]:
-            gx = _conv3x3_call(gy, weight, weight.shape[1], True, prec=ctx.prec)
-        if ours_w and ctx.needs_input_grad[1]:
-            gw = _conv3x3_wrw_call(x, gy, weight.shape, ctx.prec)
-        need_x, need_w = ctx.needs_input_grad[0] and gx is None, ctx.needs_input_grad[1] and gw is None
-        if need_x or need_w:
-            sx, sw, _ = torch.ops.aten.convolution_backward(gy, x, weight, None, stride, padding, dilation, False, [0, 0], 1,
-                                                            [need_x, need_w, False])
-            gx = sx if need_x else gx
-            gw = sw if need_w else gw
+        if ctx.ours:
+            if need_x:
+                gx = _conv3x3_call(gy, weight, weight.shape[1], True, prec=ctx.prec)
+            if need_w:
+                gw = _conv3x3_weight_grad(x, gy, weight, ctx.prec, ctx.conf)
+        elif need_x or need_w:
+            gx, gw, _ = torch.ops.aten.convolution_backward(gy, x, weight, None, *ctx.conf, False, [0, 0], 1, [need_x, need_w, False])
         gb = channel_sums(gy) if ctx.needs_input_grad[2] else None
         return gx, gw, gb, None, None, None
 
