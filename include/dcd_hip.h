@@ -285,6 +285,11 @@ int dcd_head_rows_backward(void *stream, const dcd_head_rows_args *args);
  *   dcd_loss_rows_backward  grad_sums (NCOL) -> grad_pois (B*M,C; every element written), grad_pair (B*M,NP)
  *   dcd_edge_depth_backward (caller): grad_pair -> grad_kps, grad_kps3d
  *   dcd_loss_rows_finish    grad_pois += the solver's gradients (4 * grad_kps on the 2-D keypoint channels)
+ * Every output of every call is written for EVERY slot, empty ones included: kps_*, kps3d_*, both copies of rot and P_rows, and
+ * corners_pred / corners_tgt hold for an empty slot what the first annotated object gives (slot 0 of the batch if there is none),
+ * both copies of kmask are 0 there, cols is 0 there in every column, iou3d whatever dcd_iou3d makes of those corners (possibly not
+ * finite; its column and its sum take 0 instead), grad_pois and grad_pair exactly 0; dcd_loss_rows_finish leaves the rows of empty
+ * slots as they are.
  * ---------------------------------------------------------------------------------------------- */
 #define DCD_LOSS_ROWS_NCOL 25
 typedef struct dcd_loss_rows_args {

@@ -4,7 +4,7 @@ A kernel test that hands its kernel exactly-sized fresh tensors judges the value
 every device buffer of one call and judges the rest:
 
   place(cpu_tensor)   an input: the values in the middle of a slab whose two ends hold guard words
-  out(shape)          an output: the same, the payload poisoned as well
+  out(shape)          an output: the same, the payload poisoned as well (both take fp32, fp64, int32, int64 and uint8)
   scratch(nbytes)     a workspace of exactly `nbytes` poisoned bytes between guards
   check()             every guard word intact (nothing written outside a buffer), every input bit-identical to what was placed
                       (unless declared in place), every output element overwritten (no poison word survives)
@@ -19,6 +19,11 @@ one tile row of any kernel of the library.  A buffer starts GUARD + 4 floats int
 aligned, as the entry points demand, and no better (the slab itself is aligned by the allocator, GUARD floats are a multiple of
 256 bytes, the four extra floats are one odd multiple of 16), so a kernel that assumes 256-byte bases meets the weakest pointer
 the ABI accepts.  `align=256` drops the four floats for a buffer whose contract asks for that alignment.
+
+A uint8 buffer (the masks of the loss rows and of the edge solver) has a payload of `numel` BYTES.  The bytes from there to the next
+word boundary belong to the back guard: they carry the poison and are checked as guard, and inputs, "written" and "not written" are
+judged byte by byte (the poison's bytes are 0xd1, 0xd0 ^ ordinal, 0xc0, 0x7f: none is the 0 or 1 a mask holds while the arena has
+fewer than 208 buffers).  Its base follows the same rule as every other buffer's.
 
 An Arena(poison=False) zero-fills outputs and workspaces instead (guards stay): the twin of a poisoned call for entry points that
 promise bit-reproducible results, which must not depend on what their outputs and scratch held, not even in the last bit.
@@ -35,10 +40,11 @@ _WORD = {torch.float32: 1, torch.int32: 1, torch.float64: 2, torch.int64: 2}
 
 
 class _Buffer:
-    def __init__(self, name, kind, bits, slab, front, words, view):
+    def __init__(self, name, kind, bits, slab, front, words, view, nbytes=None):
         self.name, self.kind, self.bits, self.slab, self.front, self.words, self.view = name, kind, bits, slab, front, words, view
-        self.expected = None       # inputs: the placed words (int32, CPU); None for an input declared in place
-        self.written = None        # outputs: bool (words) of what the call must overwrite; the rest must keep the poison
+        self.nbytes = nbytes       # a byte tensor's payload in bytes (the rest of its last word is back guard); None: whole words
+        self.expected = None       # inputs: the placed words (int32, CPU; bytes of a byte tensor); None if declared in place
+        self.written = None        # outputs: bool (words; bytes of a byte tensor) of what the call must overwrite; the rest keeps the poison
 
 
 class Arena:
@@ -47,7 +53,7 @@ class Arena:
         self.buffers = {}
 
     # ------------------------------------------------------------------------------------------------------------ buffers
-    def _slab(self, name, kind, words, dtype, shape, align):
+    def _slab(self, name, kind, words, dtype, shape, align, nbytes=None):
         assert name not in self.buffers, "two buffers named %r" % name
         assert align in (16, 256)
         assert len(self.buffers) < 256
@@ -55,17 +61,25 @@ class Arena:
         front = GUARD + (SKEW if align == 16 else 0)
         slab = sentinel(front + words + GUARD, bits).view(torch.int32).to(self.device)
         payload = slab[front:front + words]
-        view = payload.view(dtype).view(shape) if dtype != torch.uint8 else payload.view(torch.uint8)
+        if dtype != torch.uint8:
+            view = payload.view(dtype).view(shape)
+        else:
+            view = payload.view(torch.uint8) if nbytes is None else payload.view(torch.uint8)[:nbytes].view(shape)
         if self.device.type == "cuda":
             at = view.data_ptr() if words else slab.data_ptr() + 4 * front
             assert at % align == 0 and (align != 16 or at % 32 != 0), "%s: base %#x is not the alignment asked for" % (name, at)
-        buf = self.buffers[name] = _Buffer(name, kind, bits, slab, front, words, view)
+        buf = self.buffers[name] = _Buffer(name, kind, bits, slab, front, words, view, nbytes)
         return buf
 
     def place(self, tensor, name, inplace=False, align=16):
-        """Device view holding `tensor` (CPU; fp32, fp64, int32 or int64).  inplace: the call may write it (residual == output, a
-        running buffer): its payload is then not compared."""
+        """Device view holding `tensor` (CPU; fp32, fp64, int32, int64 or uint8).  inplace: the call may write it (residual ==
+        output, a running buffer): its payload is then not compared."""
         t = tensor.detach().contiguous()
+        if t.dtype == torch.uint8:
+            buf = self._slab(name, "input", (t.numel() + 3) // 4, t.dtype, tuple(t.shape), align, nbytes=t.numel())
+            buf.view.copy_(t)
+            buf.expected = None if inplace else t.reshape(-1).clone()
+            return buf.view
         words = t.numel() * _WORD[t.dtype]
         buf = self._slab(name, "input", words, t.dtype, tuple(t.shape), align)
         buf.view.copy_(t)
@@ -79,10 +93,13 @@ class Arena:
         numel = 1
         for s in shape:
             numel *= s
-        buf = self._slab(name, "output", numel * _WORD[dtype], dtype, shape, align)
+        if dtype == torch.uint8:
+            buf = self._slab(name, "output", (numel + 3) // 4, dtype, shape, align, nbytes=numel)
+        else:
+            buf = self._slab(name, "output", numel * _WORD[dtype], dtype, shape, align)
         if written is not None:
             assert tuple(written.shape) == shape and written.dtype == torch.bool
-            buf.written = written.reshape(-1).repeat_interleave(_WORD[dtype])
+            buf.written = written.reshape(-1).repeat_interleave(1 if dtype == torch.uint8 else _WORD[dtype])
         if not self.poison:
             buf.view.zero_() if written is None else buf.view.masked_fill_(written.to(self.device), 0)
         return buf.view
@@ -105,6 +122,9 @@ class Arena:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         for buf in self.buffers.values():
+            if buf.nbytes is not None:
+                self._check_bytes(buf, what)
+                continue
             slab = buf.slab.cpu().view(torch.float32)
             poisoned = same_bits(slab, sentinel(slab.numel(), buf.bits))
             end = buf.front + buf.words
@@ -132,3 +152,34 @@ class Arena:
                 if bad.any():
                     raise AssertionError("%s: output %r written outside its region: %d words, the first at float offset %d" % (
                         what, buf.name, int(bad.sum()), int(torch.nonzero(bad)[0])))
+
+    def _check_bytes(self, buf, what):
+        """`check` for a byte tensor: the same four judgements with the byte as the unit; offsets are in bytes from the payload."""
+        slab = buf.slab.cpu()
+        got = slab.view(torch.uint8)
+        poisoned = got == sentinel(slab.numel(), buf.bits).view(torch.uint8)
+        start = 4 * buf.front
+        end = start + buf.nbytes
+        for side, lo, hi in (("front", 0, start), ("back", end, got.numel())):
+            bad = ~poisoned[lo:hi]
+            if bad.any():
+                first = lo + int(torch.nonzero(bad)[0])
+                raise AssertionError("%s: %s guard of %s %r overwritten: %d bytes, the first at byte offset %d from the buffer's "
+                                     "start (now %#04x)" % (what, side, buf.kind, buf.name, int(bad.sum()), first - start, int(got[first])))
+        payload = got[start:end]
+        if buf.kind == "input" and buf.expected is not None:
+            bad = payload != buf.expected
+            if bad.any():
+                raise AssertionError("%s: input %r changed: %d bytes, the first at byte offset %d" % (
+                    what, buf.name, int(bad.sum()), int(torch.nonzero(bad)[0])))
+        if buf.kind == "output" and self.poison:
+            kept = poisoned[start:end]
+            must = buf.written if buf.written is not None else torch.ones(buf.nbytes, dtype=torch.bool)
+            bad = kept & must
+            if bad.any():
+                raise AssertionError("%s: output %r not written: %d bytes keep the poison, the first at byte offset %d" % (
+                    what, buf.name, int(bad.sum()), int(torch.nonzero(bad)[0])))
+            bad = ~kept & ~must
+            if bad.any():
+                raise AssertionError("%s: output %r written outside its region: %d bytes, the first at byte offset %d" % (
+                    what, buf.name, int(bad.sum()), int(torch.nonzero(bad)[0])))

@@ -121,6 +121,105 @@ def test_a_nan_handed_on_from_another_buffers_guard_is_refused():
     assert torch.isnan(y.view.view(-1)[:4]).all()
 
 
+def honest_byte_call(poison=True):
+    """kmask = mask & other written like a kernel would, on byte tensors whose sizes are no multiple of a word (7 and 10 bytes)
+    and one that is (8); `flags` only where declared."""
+    ar = A.Arena(CPU, poison=poison)
+    g = torch.Generator().manual_seed(5)
+    m = ar.place(torch.randint(0, 2, (7,), generator=g, dtype=torch.uint8), "mask")
+    o = ar.place(torch.randint(0, 2, (7,), generator=g, dtype=torch.uint8), "other", inplace=True)
+    k = ar.out((7,), "kmask", dtype=torch.uint8)
+    k8 = ar.out((2, 4), "kmask8", dtype=torch.uint8)
+    part = torch.zeros(2, 5, dtype=torch.bool)
+    part[:, 1:3] = True
+    f = ar.out((2, 5), "flags", dtype=torch.uint8, written=part)
+    k.copy_(m & o)
+    k8.fill_(1)
+    f[:, 1:3] = 0
+    o.zero_()
+    return ar
+
+
+def test_byte_tensors_layout():
+    """A uint8 buffer: `numel` bytes of payload on the base every buffer gets (16 bytes past a multiple of 256), the rest of its
+    last word poisoned guard."""
+    ar = honest_byte_call()
+    for name, nbytes, words in (("mask", 7, 2), ("other", 7, 2), ("kmask", 7, 2), ("kmask8", 8, 2), ("flags", 10, 3)):
+        b = ar.buffers[name]
+        assert b.view.dtype == torch.uint8 and b.view.numel() == nbytes and b.nbytes == nbytes and b.words == words
+        assert b.slab.numel() == A.GUARD + A.SKEW + words + A.GUARD
+        assert b.view.data_ptr() - b.slab.data_ptr() == 4 * (A.GUARD + A.SKEW)
+        pad = b.slab.view(torch.uint8)[4 * b.front + nbytes:4 * (b.front + words)]
+        assert torch.equal(pad, sentinel(words, b.bits).view(torch.uint8)[nbytes:])
+    fresh = A.Arena(CPU)
+    k = fresh.out((7,), "kmask", dtype=torch.uint8)
+    assert torch.equal(k, sentinel(2, NAN_BITS).view(torch.uint8)[:7]) and not ((k == 0) | (k == 1)).any()   # no poison byte is a mask value
+    zero = A.Arena(CPU, poison=False)
+    assert (zero.out((7,), "kmask", dtype=torch.uint8) == 0).all()
+    assert (zero.buffers["kmask"].slab.view(torch.uint8)[4 * zero.buffers["kmask"].front + 7] != 0)        # the pad byte stays guard
+
+
+@pytest.mark.parametrize("poison", [True, False])
+def test_an_honest_byte_call_passes(poison):
+    honest_byte_call(poison).check("honest bytes")
+
+
+@pytest.mark.parametrize("name", ["mask", "other", "kmask", "flags"])
+def test_a_write_into_the_pad_bytes_of_the_last_word_is_a_back_guard_overrun(name):
+    """A kernel that stores its byte mask as whole words (or runs one element over) hits the bytes between `numel` and the word
+    boundary: back guard, named by its byte offset.  Each pad byte on its own, the first word behind, and the byte in front."""
+    nbytes = honest_byte_call().buffers[name].nbytes
+    for at in range(nbytes, 4 * ((nbytes + 3) // 4)):
+        ar = honest_byte_call()
+        b = ar.buffers[name]
+        b.slab.view(torch.uint8)[4 * b.front + at] = 1
+        with pytest.raises(AssertionError, match=r"back guard of \w+ '%s' overwritten: 1 bytes, the first at byte offset %d " % (name, at)):
+            ar.check("pad byte")
+    ar = honest_byte_call()
+    b = ar.buffers[name]
+    b.slab[b.front + b.words] ^= 1
+    with pytest.raises(AssertionError, match=r"back guard of \w+ '%s' overwritten: 1 bytes, the first at byte offset %d " % (name, 4 * b.words)):
+        ar.check("word behind")
+    ar = honest_byte_call()
+    b = ar.buffers[name]
+    b.slab.view(torch.uint8)[4 * b.front - 1] = 0
+    with pytest.raises(AssertionError, match=r"front guard of \w+ '%s' overwritten: 1 bytes, the first at byte offset -1 " % name):
+        ar.check("byte in front")
+
+
+def test_one_changed_input_byte_is_refused():
+    ar = honest_byte_call()
+    ar.buffers["mask"].view[5] ^= 1
+    with pytest.raises(AssertionError, match="input 'mask' changed: 1 bytes, the first at byte offset 5"):
+        ar.check("changed byte")
+    ar = honest_byte_call()
+    ar.buffers["other"].view.fill_(9)                                    # declared in place
+    ar.check("in place bytes")
+
+
+def test_one_unwritten_output_byte_is_refused():
+    """One byte of a word left at the poison while its three neighbours were written: a word-wise check would pass it."""
+    ar = honest_byte_call()
+    b = ar.buffers["kmask"]
+    b.view[6] = sentinel(2, b.bits).view(torch.uint8)[6]
+    with pytest.raises(AssertionError, match="output 'kmask' not written: 1 bytes keep the poison, the first at byte offset 6"):
+        ar.check("left byte")
+    ar = honest_byte_call()
+    b = ar.buffers["kmask8"]
+    b.view[0, 1] = sentinel(2, b.bits).view(torch.uint8)[1]
+    with pytest.raises(AssertionError, match="output 'kmask8' not written: 1 bytes keep the poison, the first at byte offset 1"):
+        ar.check("left byte")
+    ar = honest_byte_call()
+    b = ar.buffers["flags"]
+    b.view[1, 2] = sentinel(3, b.bits).view(torch.uint8)[7]
+    with pytest.raises(AssertionError, match="output 'flags' not written: 1 bytes keep the poison, the first at byte offset 7"):
+        ar.check("left byte")
+    ar = honest_byte_call()
+    ar.buffers["flags"].view[1, 3] = 0                                   # ... and a byte written outside the declared block
+    with pytest.raises(AssertionError, match="output 'flags' written outside its region: 1 bytes, the first at byte offset 8"):
+        ar.check("outside")
+
+
 def test_a_changed_input_is_refused_unless_declared_in_place():
     ar = honest_call()
     ar.buffers["x"].view[2, 4, 6] *= -1.0                                # one sign bit
