@@ -28,7 +28,9 @@ Evaluation over a split has a FINITE plan of its own: `EvalPlan(size, batch_size
 [k B, min((k + 1) B, size)) in file order -- the last batch may be short, nothing wraps around, nothing flips -- and
 `EvalBatches(files, pipeline, batch_size, workers=None)` decodes them in a thread pool; `EvalPrefetcher` is the `Prefetcher` that
 stops at the last batch; `eval_batches(files, pipeline, batch_size, workers=None, keep_frames=False)` is the two together, as the
-passes walk them; `keep_frames` is the pipeline's keyword: the targets then carry the staged uint8 frames for the renderer."""
+passes walk them; `keep_frames` is the pipeline's keyword: the targets then carry the staged uint8 frames for the renderer.
+`mirrored=True` (test-time augmentation) makes batch k twice as long: its B images as they are, then the same B mirrored, the
+frames staged once and the samples of the second half through `flip_sample` (the pipeline's `frame_of`)."""
 import random
 from concurrent.futures import ThreadPoolExecutor
 
@@ -172,11 +174,11 @@ class EvalBatches:
     """`get(k) -> (images, targets)` of `EvalPlan`'s batch k through a `DeviceInputPipeline(is_train=False)`; the frames are read
     and decoded by `default_workers(workers)` threads."""
 
-    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False):
+    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False, mirrored=False):
         if pipeline.is_train:
             raise ValueError("evaluation needs a DeviceInputPipeline(is_train=False): it never flips")
         self.files, self.pipeline, self.batch_size, self.is_train = files, pipeline, int(batch_size), False
-        self.keep_frames = bool(keep_frames)
+        self.keep_frames, self.mirrored = bool(keep_frames), bool(mirrored)
         self.plan = EvalPlan(len(files), batch_size)
         self._pool = ThreadPoolExecutor(max_workers=default_workers(workers))
 
@@ -194,7 +196,12 @@ class EvalBatches:
         indices, _ = self.plan(k)
         read = list(self._pool.map(self._read, indices))
         extra = {"keep_frames": True} if self.keep_frames else {}
-        return self.pipeline([f for f, _ in read], [s for _, s in read], img_ids=[self.files.img_id(i) for i in indices], **extra)
+        frames, samples, ids = [f for f, _ in read], [s for _, s in read], [self.files.img_id(i) for i in indices]
+        if self.mirrored:                                              # the B frames as they are, then the same B mirrored
+            B = len(frames)
+            return self.pipeline(frames, samples + samples, img_ids=ids + ids, flip=[False] * B + [True] * B,
+                                 frame_of=list(range(B)) * 2, **extra)
+        return self.pipeline(frames, samples, img_ids=ids, **extra)
 
     def close(self):
         self._pool.shutdown(wait=True)
@@ -216,8 +223,9 @@ class eval_batches:
 
     Leaving the `with` block, by its end or by an exception, shuts the thread pool down."""
 
-    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False):
-        self.source = EvalBatches(files, pipeline, batch_size, workers, keep_frames)
+    def __init__(self, files, pipeline, batch_size, workers=None, keep_frames=False, mirrored=False):
+        self.source = EvalBatches(files, pipeline, batch_size, workers, keep_frames, mirrored) if mirrored else \
+            EvalBatches(files, pipeline, batch_size, workers, keep_frames)
         self._batches = EvalPrefetcher(self.source, pipeline.device)
 
     def __enter__(self):

@@ -67,9 +67,11 @@ class DeviceInputPipeline:
             return [False] * n
         return [self._rng.random() < self.flip_p for _ in range(n)]
 
-    def _pack(self, frames, flags):
-        """Frames -> (pinned buffer slot, used bytes).  Layout: (B, 5) int64 records, then the images, each packed HWC."""
-        B = len(frames)
+    def _pack(self, frames, flags, frame_of=None):
+        """Frames -> (pinned buffer slot, used bytes).  Layout: (B, 5) int64 records, then the images, each packed HWC.
+        frame_of: None, one record per frame in order; or, for every record, the index of the frame it reads: a record names its
+        pixels by byte offset, so two records (a frame and its mirrored view) share one copy of them."""
+        B = len(frames) if frame_of is None else len(frame_of)
         arrays, offsets = [], []
         nbytes = -(-B * _REC * 8 // _ALIGN) * _ALIGN
         for i, f in enumerate(frames):
@@ -90,26 +92,36 @@ class DeviceInputPipeline:
             slot.buf = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
         view = slot.buf.numpy()
         rec = view[:B * _REC * 8].view(np.int64).reshape(B, _REC)
-        for i, (a, off) in enumerate(zip(arrays, offsets)):
-            h, w = a.shape[:2]
-            rec[i] = (off, 3 * w, h, w, int(bool(flags[i])))
-            np.copyto(view[off:off + a.size].reshape(h, w, 3), a)
+        for a, off in zip(arrays, offsets):
+            np.copyto(view[off:off + a.size].reshape(a.shape), a)
+        for i, j in enumerate(range(B) if frame_of is None else frame_of):
+            h, w = arrays[j].shape[:2]
+            rec[i] = (offsets[j], 3 * w, h, w, int(bool(flags[i])))
         return slot, nbytes
 
-    def __call__(self, frames, samples, img_ids=None, flip=None, stream=None, keep_frames=False):
-        """keep_frames: every target also carries "frames" -- the staged uint8 buffer on the device, `_pack`'s layout, the same
+    def __call__(self, frames, samples, img_ids=None, flip=None, stream=None, keep_frames=False, frame_of=None):
+        """frame_of: None, or for each of the R samples the index of its frame in `frames`: R images come back from len(frames)
+        staged frames, each staged once however many samples name it (a frame and its mirrored view, as the evaluation with
+        test-time augmentation asks for them: `EvalBatches(mirrored=True)`); every target then also carries "image_size", the
+        image's own (w, h) on the host.
+        keep_frames: every target also carries "frames" -- the staged uint8 buffer on the device, `_pack`'s layout, the same
         tensor for all B -- "frame_records", its (B, 5) int64 record table (a view of its head), and "frame_size", the image's own
         (w, h) on the host: what `ops.render_detections` draws on.  Without the flag the staged buffer is let go as before."""
-        B = len(frames)
+        if frame_of is not None:
+            frame_of = [int(j) for j in frame_of]
+            if len(frames) == 0 or any(not 0 <= j < len(frames) for j in frame_of):
+                raise ValueError("frame_of %s names a frame outside 0 .. %d" % (frame_of, len(frames) - 1))
+        B = len(frames) if frame_of is None else len(frame_of)
         if B == 0 or len(samples) != B:
             raise ValueError("%d frames for %d samples" % (B, len(samples)))
-        for i, (f, s) in enumerate(zip(frames, samples)):
+        of_sample = frames if frame_of is None else [frames[j] for j in frame_of]
+        for i, (f, s) in enumerate(zip(of_sample, samples)):
             if tuple(int(v) for v in s["image_size"]) != (int(f.shape[1]), int(f.shape[0])):
                 raise ValueError("sample %d: image_size %s, frame is %d x %d" % (i, tuple(s["image_size"]), f.shape[1], f.shape[0]))
         flags = self.draw_flips(B) if flip is None else [bool(v) for v in flip]
         if len(flags) != B:
             raise ValueError("%d flip flags for %d frames" % (len(flags), B))
-        slot, nbytes = self._pack(frames, flags)
+        slot, nbytes = self._pack(frames, flags) if frame_of is None else self._pack(frames, flags, frame_of)
         L = _lib.lib()
         with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
             if self._table is None:
@@ -123,9 +135,12 @@ class DeviceInputPipeline:
                                                self._table.data_ptr(), B, self.in_h, self.in_w, int(self.to_bgr), images.data_ptr()),
                        "dcd_preprocess_images")
             targets = encode_targets([flip_sample(s) if f else s for s, f in zip(samples, flags)], self.cfg, self.device, img_ids)
+            if frame_of is not None:
+                for t, s in zip(targets, samples):
+                    t.add_field("image_size", tuple(int(v) for v in s["image_size"]))
             if keep_frames:
                 records = staged[:B * _REC * 8].view(torch.int64).view(B, _REC)
-                for t, f in zip(targets, frames):
+                for t, f in zip(targets, of_sample):
                     t.add_field("frames", staged)
                     t.add_field("frame_records", records)
                     t.add_field("frame_size", (int(f.shape[1]), int(f.shape[0])))

@@ -22,12 +22,20 @@ copied out once per batch and PNG-encoded by a thread pool.  Rows under TEST.DET
 whose score is not above TEST.VISUALIZE_THRESHOLD are not drawn; with `gmw=` the pictures show the detector's rows.
 
     python -m dcd_amd.engine.inference --root DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
-                                       [--gmw-ckpt FILE [--gmw-batch N]] [--render-dir DIR [--render-keypoints]] [KEY VALUE ...]
+                                       [--gmw-ckpt FILE [--gmw-batch N]] [--render-dir DIR [--render-keypoints]]
+                                       [--tta [--tta-match 2d|bev|3d] [--tta-thresh X] [--tta-unmatched X]] [KEY VALUE ...]
 
 evaluates a saved checkpoint (or, with --gmw-ckpt, a detector and a GMW checkpoint together) on its own.  `--split test` reads
 `ImageSets/test.txt`, the images and `calib` only and writes one result file per id, in `inference/data` and, with --gmw-ckpt,
 in `inference/kitti_results_for_eval`: the files of a leaderboard entry.  Nothing is scored then and the printed result is `{}`
-or `{"gmw": {}}`.  `DATASETS.INFER_ON_RIGHT_IMG True` runs either kind of split on `image_3` with `P3`."""
+or `{"gmw": {}}`.  `DATASETS.INFER_ON_RIGHT_IMG True` runs either kind of split on `image_3` with `P3`.
+
+With `tta=` (a `TTASpec`; `--tta`, or DATASETS.USE_TTA True for the default spec) the batched pass sees every image twice, as it is
+and mirrored: the 2 B records of a batch name B staged frames, the decode runs on 2 B images with each view's own P, and one
+launch (`ops.tta_merge_detections`) un-mirrors the second view's rows, matches them to the first's and fuses the pairs, before
+TEST.USE_NMS and everything after it.  A detection the mirrored view does not confirm keeps its box and loses part of its score;
+a detection only the mirrored view has is dropped, because the key points that GMW and the records need exist in the frame's own
+view only."""
 import logging
 import os
 
@@ -36,6 +44,51 @@ import torch
 
 from dcd_amd.engine.passes import load_detector, load_gmw, parse_overrides, restored_modes
 from dcd_amd.eval import kitti_annos, kitti_ap
+
+
+class TTASpec:
+    """How the mirrored view's detections are merged into the frame's (DESIGN.md "Mirrored-view test-time augmentation";
+    `ops.tta_merge_detections`): mode, the overlap a pair is matched by ('2d', 'bev' or '3d'); match_thresh in [0, 1), the overlap a
+    pair must exceed; unmatched_scale in [0, 1], what the scores of a candidate without a partner are multiplied by."""
+
+    def __init__(self, mode='2d', match_thresh=0.5, unmatched_scale=0.5):
+        if mode not in ('2d', 'bev', '3d'):
+            raise ValueError("TTA match mode %r: one of '2d', 'bev', '3d'" % (mode,))
+        match_thresh, unmatched_scale = float(match_thresh), float(unmatched_scale)
+        if not 0.0 <= match_thresh < 1.0:
+            raise ValueError("TTA match threshold %r: 0 <= threshold < 1" % (match_thresh,))
+        if not 0.0 <= unmatched_scale <= 1.0:
+            raise ValueError("TTA unmatched scale %r: 0 <= scale <= 1" % (unmatched_scale,))
+        self.mode, self.match_thresh, self.unmatched_scale = mode, match_thresh, unmatched_scale
+
+    def __repr__(self):
+        return "TTASpec(mode=%r, match_thresh=%r, unmatched_scale=%r)" % (self.mode, self.match_thresh, self.unmatched_scale)
+
+    def __eq__(self, other):
+        return isinstance(other, TTASpec) and repr(self) == repr(other)
+
+    __hash__ = None
+
+
+def resolve_tta(cfg, tta=None):
+    """The spec a pass runs with: `tta` when given, the default spec when DATASETS.USE_TTA is set, else None (no TTA code runs).
+    DATASETS.TTA_AUG_PARAMS keeps its one meaning -- more than one entry is the reference's multi-scale resize, which the
+    input pipeline refuses -- and its probability entry is not read: with TTA every image is seen both ways."""
+    if tta is not None:
+        if not isinstance(tta, TTASpec):
+            raise TypeError("tta: a TTASpec or None, not %r" % (tta,))
+        return tta
+    return TTASpec() if cfg is not None and bool(cfg.DATASETS.USE_TTA) else None
+
+
+def _widths(targets, device, cache):
+    """(B,) int32 on the device: every image's own width, from the targets' host-side "image_size"; one copy per distinct set of
+    values (cached by value, as `PostProcessor._image_table`)."""
+    host = np.array([int(t.get_field("image_size")[0]) for t in targets], np.int32)
+    key = (host.tobytes(), str(device))
+    if cache.get("key") != key:
+        cache["key"], cache["widths"] = key, torch.as_tensor(host).to(device, non_blocking=True)
+    return cache["widths"]
 
 
 def keep_prefix(raw_scores, threshold):
@@ -59,14 +112,16 @@ def _records(rows, k2, k3, cat="Car"):
              'score': r[13:14], 'cat': cat} for i, r in enumerate(rows)]
 
 
-def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records, refiner=None, renderer=None):
+def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, want_records, refiner=None, renderer=None, tta=None):
     """The batched loop.  Returns {img_id: records} (empty without `want_records`).  Raises NotImplementedError, before anything
     runs, when the configuration is one `decode_fused` does not cover.  refiner: a `gmw.RecordRefiner`; the decode then always
     leaves the key points on the device, every batch's kept rows are handed to it (`refiner.add`, a batch late, with the host
     rows appended to `refiner.host_rows` / `refiner.host_ids` for the writer), and the key points go to the host only with
     `want_records`.  renderer: a `dcd_amd.engine.render.Renderer`; the walker then keeps the staged frames with the targets and every
     batch is drawn right after its decode (`renderer.add`); a renderer that draws key points makes the decode leave them on the
-    device as the refiner does."""
+    device as the refiner does.  tta: a `TTASpec`; every batch then goes through the model as 2 B images -- the frames and their
+    mirrored views, staged once -- and `ops.tta_merge_detections` brings the 2 B decoded blocks back to B before TEST.USE_NMS and
+    everything else, which see merged blocks with the same prefix contract."""
     from dcd_amd.data.batches import eval_batches
     pp, predictor = model.heads.post_processor, model.heads.predictor
     spec = pp.decode_spec()                                            # refuses here, before the walker and its threads exist
@@ -101,13 +156,26 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
     predictor.sparse_eval_heads = True
     try:
         keep = {"keep_frames": True} if renderer is not None else {}
+        if tta is not None:
+            from dcd_amd import ops
+            keep["mirrored"] = True
+            width_cache = {}
         device_records = want_records or refiner is not None or (renderer is not None and renderer.keypoints)
         with eval_batches(files, pipeline, batch_size, workers, **keep) as walk:
             pending = None
             for k, indices, images, targets in walk:
                 feats = model.backbone(images)
                 preds = predictor(feats, targets)
-                rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=device_records)
+                if tta is None:
+                    rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=device_records)
+                else:
+                    rows, aux, recs = pp.decode_fused(preds, targets, test=model.test, records=device_records, nms=False)
+                    targets = targets[:len(indices)]                     # the frames as they are: what everything below works on
+                    k2, k3 = recs if recs is not None else (None, None)
+                    rows, aux, k2, k3 = ops.tta_merge_detections(rows, aux, k2, k3, K, _widths(targets, rows.device, width_cache), tta.mode,
+                                                                 tta.match_thresh, threshold, tta.unmatched_scale)[:4]
+                    rows, aux, k2, k3 = pp.nms_fused(rows, aux, k2, k3, K)
+                    recs = (k2, k3) if recs is not None else None
                 if renderer is not None:
                     renderer.add(k, [files.img_id(i) for i in indices], targets[0].get_field("frames"), rows, aux, recs,
                                  pp._image_table(targets, rows.device), targets)
@@ -126,7 +194,7 @@ def _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, w
 
 
 def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_size=1, workers=None, gen_out_dir=None, gmw=None,
-              gmw_batch=256, render_dir=None, render_keypoints=False):
+              gmw_batch=256, render_dir=None, render_keypoints=False, tta=None):
     """model: a `KeypointDetector`; files: a `KittiFiles`; pipeline: a `DeviceInputPipeline(is_train=False)`.
     batch_size = 1 and gen_out_dir = None: one image per model call, as the reference.  Otherwise the batched pass (see the
     module docstring); gen_out_dir: where the same pass leaves `gen_data_infer.json`.  A configuration the fused decode does
@@ -139,6 +207,11 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     render_dir: where the pass leaves one picture per id, `<render_dir>/<id>.png` (`dcd_amd.engine.render`): the pass is then always
     the batched one and, as with `gmw`, a configuration the fused decode refuses is an error.  render_keypoints: draw the dense key
     points as well.  An unlabelled split draws no ground truth.  With render_dir = None nothing of this is launched, allocated or kept.
+    tta: a `TTASpec`, or None with DATASETS.USE_TTA True for the default one: mirrored-view test-time augmentation.  The pass is
+    then always the batched one; every image is decoded as it is and mirrored (the mirrored records name the same staged pixels),
+    and the two views' candidates are merged on the device before TEST.USE_NMS, `gmw`, `gen_out_dir` and `render_dir`, which work
+    on the merged blocks unchanged.  A configuration the fused decode refuses is an error.  With tta = None and USE_TTA False
+    nothing of this is launched, allocated or packed.
     Returns {metric: the dict of `kitti_ap.official_eval`}.
     A `files` whose `has_labels` is false (KITTI's `test` split; an object without the attribute counts as labelled) goes through
     the same pass and only leaves its files behind: see `finish_pass`."""
@@ -152,7 +225,8 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
     ids = [files.img_id(i) for i in range(len(files))]
     with restored_modes(model, gmw), torch.no_grad():
         model.eval()
-        batched = batch_size > 1 or gen_out_dir is not None or gmw is not None or render_dir is not None
+        tta = resolve_tta(getattr(model, "cfg", None), tta)                # (a model without a configuration: the argument alone)
+        batched = batch_size > 1 or gen_out_dir is not None or gmw is not None or render_dir is not None or tta is not None
         refiner = renderer = None
         if render_dir is not None:
             from dcd_amd.engine.render import Renderer
@@ -165,6 +239,8 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
         if batched:
             try:
                 extra = {"renderer": renderer} if renderer is not None else {}
+                if tta is not None:
+                    extra["tta"] = tta
                 try:
                     infer_data = _batched_pass(model, files, pipeline, predict_folder, batch_size, workers, gen_out_dir is not None,
                                                refiner, **extra)
@@ -179,6 +255,9 @@ def inference(model, files, pipeline, output_folder, metrics=("R40",), batch_siz
                     raise NotImplementedError("inference(gmw=...) needs the fused decode, which refuses this configuration: %s" % e)
                 if renderer is not None:
                     raise NotImplementedError("inference(render_dir=...) needs the fused decode, which refuses this configuration: %s" % e)
+                if tta is not None:
+                    raise NotImplementedError("inference with TTA (tta=... / DATASETS.USE_TTA) needs the fused decode, which refuses "
+                                              "this configuration: %s" % e)
                 logger.info("batched evaluation is not available (%s): one image per call", e)
                 batched = False
                 if gen_out_dir is not None:
@@ -234,6 +313,29 @@ def finish_pass(files, ids, output_folder, metrics, device, refined=None):
     return results
 
 
+def add_tta_arguments(ap):
+    ap.add_argument("--tta", action="store_true", help="mirrored-view test-time augmentation: decode every image as it is and "
+                    "mirrored, merge the two on the device (also switched on by DATASETS.USE_TTA True)")
+    ap.add_argument("--tta-match", choices=("2d", "bev", "3d"), default=None, help="with --tta: the overlap pairs are matched by (2d)")
+    ap.add_argument("--tta-thresh", type=float, default=None, help="with --tta: the overlap a pair must exceed (0.5)")
+    ap.add_argument("--tta-unmatched", type=float, default=None, help="with --tta: the factor on the scores of a detection the "
+                    "mirrored view does not confirm (0.5)")
+
+
+def tta_from_arguments(ap, args):
+    """The `TTASpec` of the command line, or None without --tta (DATASETS.USE_TTA then decides, with the default spec)."""
+    given = {k: v for k, v in (("mode", args.tta_match), ("match_thresh", args.tta_thresh), ("unmatched_scale", args.tta_unmatched))
+             if v is not None}
+    if not args.tta:
+        if given:
+            ap.error("--tta-match / --tta-thresh / --tta-unmatched need --tta")
+        return None
+    try:
+        return TTASpec(**given)
+    except ValueError as e:
+        ap.error(str(e))
+
+
 def main(argv=None):
     """`python -m dcd_amd.engine.inference --root KITTI_DIR --split val --ckpt FILE --output-dir OUT [--batch N] [--gen-data]
     [--gmw-ckpt FILE [--gmw-batch N]] [--render-dir DIR [--render-keypoints]] [KEY VALUE ...]`: evaluate a saved checkpoint (a file, or a directory with `last_checkpoint`) on one GPU."""
@@ -257,10 +359,12 @@ def main(argv=None):
     ap.add_argument("--render-dir", default=None, help="also leave one picture per image here, <id>.png: detections over ground truth "
                     "and a bird's-eye panel, drawn on the device in the same pass")
     ap.add_argument("--render-keypoints", action="store_true", help="with --render-dir: draw the dense key points too")
+    add_tta_arguments(ap)
     ap.add_argument("opts", nargs="*", help="configuration overrides: KEY VALUE ...")
     args = ap.parse_args(argv)
     if args.render_keypoints and not args.render_dir:
         ap.error("--render-keypoints needs --render-dir")
+    tta = tta_from_arguments(ap, args)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
     cfg = get_cfg(opts=parse_overrides(args.opts))
     device = torch.device("cuda", torch.cuda.current_device())
@@ -271,7 +375,7 @@ def main(argv=None):
     gen_out_dir = os.path.join(args.output_dir, "gen_data") if args.gen_data else None
     results = inference(model, files, pipeline, os.path.join(args.output_dir, "inference"), metrics=tuple(cfg.TEST.METRIC),
                         batch_size=args.batch, workers=args.workers, gen_out_dir=gen_out_dir, gmw=gmw, gmw_batch=args.gmw_batch,
-                        render_dir=args.render_dir, render_keypoints=args.render_keypoints)
+                        render_dir=args.render_dir, render_keypoints=args.render_keypoints, tta=tta)
 
     def plain(v):
         return {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else (v.tolist() if hasattr(v, "tolist") else v)

@@ -265,7 +265,7 @@ def collect_gmw_records(model, batches, iterations, start=0, capacity=None, cfg=
 
 
 def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, arguments, output_dir, step=None, log_every=10, val=None,
-             val_batch_size=1, val_gmw=None, gmw_records=False, val_render_dir=None, val_render_keypoints=False):
+             val_batch_size=1, val_gmw=None, gmw_records=False, val_render_dir=None, val_render_keypoints=False, val_tta=None):
     """batches: a source of data/batches.py (or a `Prefetcher` around one).  step: `step(images, targets) -> (loss_dict,
     log_loss_dict)`, e.g. a `GraphedTrainStep`; by default `train_step` with SOLVER.GRAD_NORM_CLIP.  val: (files, pipeline) of
     `engine.inference.inference`, run after the final checkpoint; its result comes back as arguments["eval"].
@@ -282,7 +282,9 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     and `gen_data_train.json` is not written.  "json" writes the file as well, from one bulk copy.  A configuration the record
     kernel refuses raises NotImplementedError before the first batch.  False (the default): the pass and the file as before.
     val_render_dir: the evaluation also leaves one picture per validation image there (`inference(render_dir=...)`, the batched
-    pass whatever val_batch_size is); val_render_keypoints draws the dense key points too."""
+    pass whatever val_batch_size is); val_render_keypoints draws the dense key points too.
+    val_tta: an `engine.inference.TTASpec`, handed to `inference(tta=...)`: the evaluation merges every image's detections with its
+    mirrored view's (the batched pass whatever val_batch_size is); None leaves DATASETS.USE_TTA to decide."""
     logger = logging.getLogger("dcd_amd.trainer")
     is_gen = bool(cfg.TEST.GENERATE_GMW)
     if cfg.SOLVER.LR_WARMUP and warmup_scheduler is None:
@@ -361,6 +363,8 @@ def do_train(cfg, model, optimizer, scheduler, warmup_scheduler, batches, argume
     if val is not None:
         from dcd_amd.engine.inference import inference
         render = {"render_dir": val_render_dir, "render_keypoints": val_render_keypoints} if val_render_dir is not None else {}
+        if val_tta is not None:
+            render["tta"] = val_tta
         if val_batch_size > 1 or val_gmw is not None:
             gen_out_dir = os.path.join(output_dir, "gen_data") if is_gen else None
             if is_gen:

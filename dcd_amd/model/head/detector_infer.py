@@ -289,12 +289,14 @@ class PostProcessor(nn.Module):
         pad = stack_field(targets, "pad_size").to(device=device, dtype=torch.float32)
         return torch.cat((pad, self._table_cache[1]), dim=1)
 
-    def decode_fused(self, predictions, targets, test=False, records=None):
+    def decode_fused(self, predictions, targets, test=False, records=None, nms=True):
         """What `forward_batch` takes -> (rows (B K, 14), aux (B K, 4), records or None) for ALL B K candidates in (image, rank)
         order, from one kernel launch after the top-K: no score threshold, no `nonzero`, no host synchronisation (the raw scores
         -- aux[:, 0] -- come out of the top-K descending per image, so the caller keeps a prefix).  aux = raw score, estimated
         depth error, confidence, arg-max index of the fusion.  records (with TEST.GENERATE_GMW, or records=True) =
         (K-normalised key points (B K, nk, 2), each row with its own image's intrinsics, 3-D key points (B K, nk, 3)).
+        nms=False leaves TEST.USE_NMS to the caller (`nms_fused`): the pass with test-time augmentation merges the two views' blocks
+        first, so that suppression sees fused boxes.
         Raises NotImplementedError for a configuration the kernel does not cover."""
         from dcd_amd import ops
         spec = self.decode_spec()
@@ -308,10 +310,17 @@ class PostProcessor(nn.Module):
         table = self._image_table(targets, vectors.device)
         want = self.generate_data if records is None else bool(records)
         rows, aux, k2, k3 = ops.decode_detections(vectors, topk, table, spec, records=want)
-        if self.nms_mode != 'none':                           # one more launch; the outputs keep the prefix contract
-            rows, aux, k2, k3, _ = ops.nms_detections(rows, aux, k2, k3, topk[0].shape[1], self.nms_mode, self.nms_thresh,
-                                                      self.det_threshold, self.nms_class_agnostic)
+        if nms:
+            rows, aux, k2, k3 = self.nms_fused(rows, aux, k2, k3, topk[0].shape[1])
         return rows, aux, ((k2, k3) if want else None)
+
+    def nms_fused(self, rows, aux, k2, k3, K):
+        """TEST.USE_NMS on blocks of K decoded rows: one more launch, the outputs keep the prefix contract; 'none' launches nothing
+        and hands the tensors back."""
+        if self.nms_mode == 'none':
+            return rows, aux, k2, k3
+        from dcd_amd import ops
+        return ops.nms_detections(rows, aux, k2, k3, K, self.nms_mode, self.nms_thresh, self.det_threshold, self.nms_class_agnostic)[:4]
 
     def _image_kpts(self, targets, pois, pred_bbox_points, pred_offset_3D):
         k2c = self.key2channel

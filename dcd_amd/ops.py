@@ -2040,6 +2040,50 @@ def nms_detections(rows, aux, k2, k3, K, mode, thresh, det_threshold, class_agno
     return outs[0], outs[1], outs[2], outs[3], overlaps
 
 
+def tta_merge_detections(rows, aux, k2, k3, K, widths, mode, match_thresh, det_threshold, unmatched_scale, want_overlaps=False):
+    """Merge every image's detections with those of its mirrored view in ONE launch (csrc/tta.hip; the rule is in DESIGN.md
+    "Mirrored-view test-time augmentation" and include/dcd_hip.h).  rows (2 B K, 14), aux (2 B K, 4), k2 (2 B K, nk, 2) / k3
+    (2 B K, nk, 3) or None -- the outputs of `decode_detections` for 2 B images: the first B blocks are the frames as they are
+    (view A), the last B the same frames mirrored (view M).  widths: (B,) int32 on the device, every image's own width.
+    Returns (rows, aux, k2, k3, src, mate, overlaps) for B blocks: the K rows of view A, each fused with its matched M row or with
+    its scores scaled by `unmatched_scale`, re-ordered by raw score so that `aux[:, 0] >= det_threshold` is a prefix of every
+    block; src / mate (B K,) int32: the A rank a row came from and the M rank it was fused with, or -1; overlaps: (B, K, K) fp32
+    of what was compared, or None.  No host synchronisation."""
+    _lib.require_cuda(rows, aux, k2, k3, widths)
+    if mode not in NMS_MODE:
+        raise ValueError("TTA match mode %r (one of %s)" % (mode, ", ".join(sorted(NMS_MODE))))
+    if (k2 is None) != (k3 is None):
+        raise ValueError("both key-point tensors or neither")
+    K = int(K)
+    rows, aux = _f32c(rows).reshape(-1, 14), _f32c(aux).reshape(-1, 4)
+    n = rows.shape[0]
+    if K < 1 or K > NMS_MAX_K or n % K or aux.shape[0] != n:
+        raise ValueError("rows %s and aux %s do not hold blocks of K = %d (1 .. %d)" % (tuple(rows.shape), tuple(aux.shape), K, NMS_MAX_K))
+    if n == 0 or (n // K) % 2:
+        raise ValueError("%d blocks of K = %d: the two views of every image make an even, positive number" % (n // K, K))
+    B = n // K // 2
+    if widths.dtype != torch.int32 or tuple(widths.shape) != (B,):
+        raise ValueError("widths is %s %s, expected (%d,) int32" % (widths.dtype, tuple(widths.shape), B))
+    widths = widths.contiguous()
+    nk = 0
+    if k2 is not None:
+        k2, k3 = _f32c(k2), _f32c(k3)
+        nk = k2.shape[1]
+        if tuple(k2.shape) != (n, nk, 2) or tuple(k3.shape) != (n, nk, 3):
+            raise ValueError("key points %s / %s for %d rows" % (tuple(k2.shape), tuple(k3.shape), n))
+    dev = rows.device
+    outs = [None if t is None else torch.empty((B * K,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in (rows, aux, k2, k3)]
+    src = torch.empty((B * K,), dtype=torch.int32, device=dev)
+    mate = torch.empty((B * K,), dtype=torch.int32, device=dev)
+    overlaps = torch.empty((B, K, K), dtype=torch.float32, device=dev) if want_overlaps else None
+    st = _lib.lib().dcd_tta_merge_detections(_lib.stream_of(rows), rows.data_ptr(), aux.data_ptr(), _lib.ptr(k2), _lib.ptr(k3),
+                                             widths.data_ptr(), B, K, nk, NMS_MODE[mode], float(match_thresh), float(det_threshold),
+                                             float(unmatched_scale), outs[0].data_ptr(), outs[1].data_ptr(), _lib.ptr(outs[2]),
+                                             _lib.ptr(outs[3]), src.data_ptr(), mate.data_ptr(), _lib.ptr(overlaps))
+    _lib.check(st, "dcd_tta_merge_detections")
+    return outs[0], outs[1], outs[2], outs[3], src, mate, overlaps
+
+
 DEPTH_METHODS = ("direct", "kpt_center", "kpt_02", "kpt_13", "soft", "hard", "mean", "edges", "oracle", "gmw")
 DEPTH_ROW = 3 + len(DEPTH_METHODS)     # valid, class, gt_z, the methods
 DEPTH_STATS = 5                        # count, sum |e|, sum e, sum e^2, non-finite estimates

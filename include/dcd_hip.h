@@ -1008,6 +1008,40 @@ int dcd_nms_detections(void *stream, const float *rows, const float *aux, const 
                        float *kpts2d_out, float *kpts3d_out, float *overlaps_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mirrored-view test-time augmentation: the detections of a frame (view A) merged with those of the same frame mirrored and
+ * decoded with the mirrored P (view M), for every image of a batch in ONE launch (csrc/tta.hip, arithmetic in csrc/tta_math.h;
+ * the rule in full is DESIGN.md "Mirrored-view test-time augmentation").
+ *   rows (2 B K, 14), aux (2 B K, 4), kpts2d (2 B K, nk, 2), kpts3d (2 B K, nk, 3): dcd_decode_detections' outputs for 2 B
+ *               images: blocks 0 .. B - 1 are view A, block B + b is view M of image b.  The key points may both be NULL.
+ *   widths (B,) int32: every image's OWN width in pixels (not the padded canvas): a row of M is un-mirrored with it, the
+ *               inverse of `flip_sample`: x1' = (W - 1) - x2, x2' = (W - 1) - x1, x' = -x, ry' = (ry < 0 ? -pi - ry : pi - ry)
+ *               wrapped into [-pi, pi], alpha' = wrap(ry' - atan2f(x', z)); float32.
+ *   candidates  of view A: the prefix with raw score aux[., 0] >= det_threshold, as dcd_nms_detections counts it; they are
+ *               visited in its order (descending final score, a tie to the lower rank, NaN last).  Eligible rows of view M: all
+ *               K whose raw score is not NaN.
+ *   matching    a candidate takes the still-unmatched eligible M row of the same integer class whose overlap with it (mode:
+ *               DCD_NMS_2D / _BEV / _3D, dcd_nms_detections' own, the A row as the frame) is > match_thresh in float64 and, rounded
+ *               to float32, the largest; a tie goes to the lower M rank.
+ *   fusing      a matched pair gives one row by score and inverse-depth-error weights (tta_math.h, tta_fuse); an unmatched
+ *               candidate has its final and raw score multiplied by unmatched_scale and keeps every other bit; a row of A below
+ *               the cut is copied; an M row without a partner is dropped.  Every output row has an A member.
+ *   rows_out (B K, 14), aux_out (B K, 4), kpts2d_out (B K, nk, 2), kpts3d_out (B K, nk, 3): per image the K rows re-ordered by
+ *               output raw score, descending, stable on A's rank, NaN last, so `aux_out[., 0] >= det_threshold` is a prefix
+ *               again; the key points are those of the row's A member.  Outputs must not alias inputs.
+ *   src_out, mate_out (B K,) int32: the A rank an output row came from, and the M rank it was fused with or -1.
+ *   overlaps_out (B, K, K) fp32 or NULL: element (a, m) = the overlap of A candidate a with the un-mirrored eligible M row m,
+ *               every other element 0.  With it every such pair is evaluated; without it only pairs of one class.
+ * One workgroup per image; no atomics, no workspace, nothing read back: two calls give the same bits.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null or aliased pointer, B < 1, K outside 1 .. 128, 2 B K > 2^31 - 1, nk
+ * outside 1 .. 128 when key points are given, only some of the four key-point pointers given, an unknown mode, match_thresh
+ * outside [0, 1) or NaN, unmatched_scale outside [0, 1] or NaN, or a NaN det_threshold.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_tta_merge_detections(void *stream, const float *rows, const float *aux, const float *kpts2d, const float *kpts3d,
+                             const int *widths, int B, int K, int nk, int mode, double match_thresh, double det_threshold,
+                             double unmatched_scale, float *rows_out, float *aux_out, float *kpts2d_out, float *kpts3d_out,
+                             int *src_out, int *mate_out, float *overlaps_out);
+
+/* ------------------------------------------------------------------------------------------------
  * The detections of a batch drawn on the device (csrc/render.hip; the raster rule is the header of csrc/render_math.h and
  * DESIGN.md 6d): per image the frame with the 2-D boxes, projected 3-D boxes, key points and labels, and beside it a square
  * bird's-eye panel, ground truth under detections, rank 0 on top.  Two launches: the primitive table, then the tiles.
