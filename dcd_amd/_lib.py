@@ -185,6 +185,9 @@ SIGNATURES = {
                               + [c_int, c_int, c_void_p, c_size_t]),
     "dcd_depth_estimates": (c_int, [c_void_p] * 8 + [ctypes.POINTER(DecodeArgs), c_void_p]),
     "dcd_depth_accumulate": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), c_int, c_int, c_void_p, c_void_p]),
+    "dcd_dis_iou_estimates": (c_int, [c_void_p] * 9 + [ctypes.POINTER(DecodeArgs), c_void_p, c_void_p]),
+    "dcd_dis_iou_accumulate": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), c_int, c_int, ctypes.POINTER(c_double),
+                               c_void_p, c_void_p]),
     "dcd_nms_detections": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_double, c_double, c_int] + [c_void_p] * 5),
     "dcd_tta_merge_detections": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_double] * 3 + [c_void_p] * 7),
     "dcd_render_slots": (c_int, [c_int] * 3),

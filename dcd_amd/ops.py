@@ -2144,6 +2144,81 @@ def depth_accumulate(est, edges, table, outside):
     _lib.check(st, "dcd_depth_accumulate")
 
 
+DIS_VARIANTS = ("full", "location", "offset", "dims", "orient") + tuple("depth:" + m for m in DEPTH_METHODS)
+DIS_METRICS = ("bev", "3d")
+DIS_ROW = 3 + len(DIS_METRICS) * len(DIS_VARIANTS)     # valid, class, gt_z, bev[15], iou3d[15]
+DIS_STATS = 6                          # count, sum IoU, sum IoU^2, hits > strict threshold, hits > loose threshold, non-finite
+DIS_GT = 9                             # offset_3D (2), locations (3), dimensions (3), rotys (1)
+DIS_BOX = 7                            # h w l x y z ry
+
+
+def dis_iou_estimates(vectors, ys, xs, classes, gt, valid, image_table, spec, gmw_z=None, want_boxes=False):
+    """The disentangled boxes of a batch of labelled objects and their overlaps with the labels in ONE launch: vectors (B, M, C)
+    head outputs at the objects' cells, ys / xs / classes / valid (B, M) as for `depth_estimates`, gt (B, M, 9) = [offset_3D (2),
+    locations (3, the box centre), dimensions (3: l h w), rotys], image_table (B, 16), spec of `PostProcessor.decode_spec`,
+    gmw_z (B, M) GMW's refined depth of every slot or None (then the `depth:gmw` variant is NaN).  Returns dis (B M, 33) =
+    [valid, class, gt_z, the BEV overlap of the fifteen `DIS_VARIANTS`, their 3-D overlap]; an empty slot's row is all zeros.
+    want_boxes=True returns (dis, boxes (B M, 16, 7)): h w l x y z ry of the label and of the fifteen variants.
+    No host synchronisation.  A configuration the kernel does not cover gives `DcdHipError` (status 1) without a launch."""
+    _lib.require_cuda(vectors, ys, xs, classes, gt, valid, image_table, gmw_z)
+    if vectors.dim() != 3:
+        raise ValueError("dis_iou_estimates: vectors is %s, expected (B, M, C)" % (tuple(vectors.shape),))
+    B, M, C = vectors.shape
+    vec, table = _f32c(vectors).reshape(B * M, C), _f32c(image_table)
+    if tuple(table.shape) != (B, DECODE_TABLE):
+        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
+    per_slot = [ys, xs, classes, valid] + ([] if gmw_z is None else [gmw_z])
+    if any(t.numel() != B * M for t in per_slot):
+        raise ValueError("dis_iou_estimates: ys, xs, classes, valid and gmw_z hold one value per slot (%d x %d)" % (B, M))
+    if gt.numel() != B * M * DIS_GT or gt.shape[-1] != DIS_GT:
+        raise ValueError("dis_iou_estimates: gt is %s, expected (%d, %d, %d)" % (tuple(gt.shape), B, M, DIS_GT))
+    ys, xs, classes, gt = _f32c(ys), _f32c(xs), _f32c(classes), _f32c(gt)
+    valid = _typed(valid, torch.uint8)
+    gmw_z = None if gmw_z is None else _f32c(gmw_z)
+    a = decode_args(spec, B, M, C)
+    dis = torch.empty((B * M, DIS_ROW), dtype=torch.float32, device=vec.device)
+    boxes = torch.empty((B * M, 1 + len(DIS_VARIANTS), DIS_BOX), dtype=torch.float32, device=vec.device) if want_boxes else None
+    st = _lib.lib().dcd_dis_iou_estimates(_lib.stream_of(vec), vec.data_ptr(), ys.data_ptr(), xs.data_ptr(), classes.data_ptr(),
+                                          gt.data_ptr(), valid.data_ptr(), table.data_ptr(), _lib.ptr(gmw_z), a, dis.data_ptr(),
+                                          _lib.ptr(boxes))
+    _lib.check(st, "dcd_dis_iou_estimates")
+    return (dis, boxes) if want_boxes else dis
+
+
+def dis_iou_tables(num_classes, n_bins, device):
+    """Zeroed running tables for `dis_iou_accumulate`: (table (num_classes, n_bins, 15, 2, 6) float64, outside (num_classes) int64)."""
+    return (torch.zeros((num_classes, n_bins, len(DIS_VARIANTS), len(DIS_METRICS), DIS_STATS), dtype=torch.float64, device=device),
+            torch.zeros((num_classes,), dtype=torch.int64, device=device))
+
+
+def dis_iou_accumulate(dis, edges, thresholds, table, outside):
+    """The rows of `dis_iou_estimates` booked into the running tables of `dis_iou_tables`, in place and in one launch: an object
+    of class c falls in bin i when edges[i] <= gt_z < edges[i + 1] and adds each overlap to the stats [count, sum IoU, sum IoU^2,
+    hits, loose hits] of cell (c, i, variant, metric); thresholds (num_classes, 2, 2) on the host: per class and metric the strict
+    and the loose threshold, a hit is IoU > threshold; a non-finite overlap raises the cell's sixth stat instead; an object in no
+    bin counts in outside[c] only.  Every cell adds its objects in slot order, so the tables have the same bits however a split is
+    cut into calls.  No host synchronisation."""
+    _lib.require_cuda(dis, table, outside)
+    edges = [float(e) for e in edges]
+    n_bins = len(edges) - 1
+    if dis.dim() != 2 or dis.shape[1] != DIS_ROW or dis.dtype != torch.float32 or not dis.is_contiguous():
+        raise ValueError("dis_iou_accumulate: dis is %s %s, expected contiguous float32 (n, %d)" % (dis.dtype, tuple(dis.shape), DIS_ROW))
+    num_classes = int(outside.shape[0]) if outside.dim() == 1 else -1
+    if (table.dtype != torch.float64 or outside.dtype != torch.int64 or not table.is_contiguous() or not outside.is_contiguous()
+            or tuple(table.shape) != (num_classes, n_bins, len(DIS_VARIANTS), len(DIS_METRICS), DIS_STATS)):
+        raise ValueError("dis_iou_accumulate: table %s %s / outside %s %s do not fit %d bins (see dis_iou_tables)"
+                         % (table.dtype, tuple(table.shape), outside.dtype, tuple(outside.shape), n_bins))
+    flat = [float(t) for per_class in thresholds for per_metric in per_class for t in per_metric]
+    if len(flat) != num_classes * len(DIS_METRICS) * 2:
+        raise ValueError("dis_iou_accumulate: %d thresholds, expected (%d classes, %d metrics, strict and loose)"
+                         % (len(flat), num_classes, len(DIS_METRICS)))
+    c_edges = (_lib.c_float * max(len(edges), 1))(*edges)
+    c_thr = (_lib.c_double * len(flat))(*flat)
+    st = _lib.lib().dcd_dis_iou_accumulate(_lib.stream_of(dis), dis.data_ptr(), int(dis.shape[0]), c_edges, n_bins, num_classes, c_thr,
+                                           table.data_ptr(), outside.data_ptr())
+    _lib.check(st, "dcd_dis_iou_accumulate")
+
+
 RENDER_ENTRY = 12          # int32 per primitive: panel, kind, x0, y0, x1, y1, thickness, r, g, b, order, glyph (csrc/render_math.h)
 _FRAME_REC = 5             # int64 per image in front of the staged frames (dcd_amd/data/input_pipeline.py, `_pack`)
 

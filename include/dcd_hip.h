@@ -973,6 +973,53 @@ int dcd_depth_accumulate(void *stream, const float *est, int n_slots, const floa
                          double *table, int64_t *outside);
 
 /* ------------------------------------------------------------------------------------------------
+ * The disentangled IoU report (csrc/dis_iou.hip, arithmetic in csrc/dis_iou_math.h on top of csrc/decode_math.h,
+ * csrc/depth_report_math.h and csrc/nms_math.h): at every labelled object, fifteen boxes in which ONE component is the
+ * prediction's and the rest is the label's, and each box's BEV and 3-D overlap with the label -- which head loses the overlap.
+ *
+ * dcd_dis_iou_estimates: one launch, one workgroup per object slot, B * M slots (args as for dcd_depth_estimates).
+ *   vectors, ys, xs, classes, valid, image_table   as for dcd_depth_estimates
+ *   gt           (B M, 9) fp32: offset_3D (2), locations (3: the box CENTRE), dimensions (3: l h w), rotys (1)
+ *   gmw_z        (B M) fp32: GMW's refined depth of the slot, or null (then NaN)
+ *   dis          (B M, 33): valid (1 or 0), class, gt_z, bev[15], iou3d[15]
+ *   boxes        (B M, 16, 7) or null: h w l x y z ry (y the bottom: columns 6:13 of a decoded row) of the label, then of the
+ *                fifteen variants; null: not written
+ * The variants, in the order of their columns (location | dimensions | yaw):
+ *    0 full      the row dcd_decode_detections writes at that cell and class, same bits | predicted | predicted roty
+ *    1 location  full's centre, the bottom from the label's h | label | label
+ *    2 offset    the predicted projected-centre offset, back-projected at the label's z | label | label
+ *    3 dims      the label's centre, the bottom from the predicted h | predicted | label
+ *    4 orient    label | label | wrap(predicted alpha + atan2(label x, label z))
+ *    5-14 depth:<m>, the ten methods of dcd_depth_estimates in their order (gmw from gmw_z): the LABEL's offset_3D
+ *                back-projected at depth d[m] | label | label
+ * The overlaps are the KITTI evaluator's (nms_math.h: nms_overlap_bev, nms_overlap_3d) with the label in the ground-truth box's
+ * role.  When one of a variant's seven numbers is not finite, or an overlap comes out non-finite, both overlaps of that variant
+ * are NaN; there is no other special case (a non-positive predicted dimension is booked as the evaluator's arithmetic makes it).
+ * An empty slot's row (and boxes) are zeros and its vector is never read.  A row depends on its own slot only.  Fixed-order sums,
+ * plain stores, no atomics: two calls give the same bits.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer (gmw_z and boxes may be null) and for everything
+ * dcd_decode_detections refuses.
+ *
+ * dcd_dis_iou_accumulate: adds the rows of one batch to running tables in device memory, one launch.
+ *   dis          (n_slots, 33) as above
+ *   edges        n_bins + 1 floats ON THE HOST, read during the call; the bin rule of dcd_depth_accumulate
+ *   thresholds   (num_classes, 2, 2) doubles ON THE HOST, read during the call: per class and metric (bev, 3d) the strict and the
+ *                loose overlap threshold, each in [0, 1]
+ *   table        (num_classes, n_bins, 15, 2, 6) fp64, zeroed by the caller before the first call: per cell the count of finite
+ *                overlaps, sum IoU, sum IoU^2, the overlaps > the strict threshold, those > the loose one (the evaluator's
+ *                comparison), and the count of non-finite overlaps
+ *   outside      (num_classes) i64, as for dcd_depth_accumulate
+ * One thread per cell walks the rows in slot order: the tables have the same bits however a split is cut into calls.
+ * Status: DCD_ERR_BAD_ARG, without a launch, for a null pointer, everything dcd_depth_accumulate refuses, and a threshold
+ * outside [0, 1] or NaN.  n_slots = 0 is DCD_OK and does nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int dcd_dis_iou_estimates(void *stream, const float *vectors, const float *ys, const float *xs, const float *classes,
+                          const float *gt, const uint8_t *valid, const float *image_table, const float *gmw_z,
+                          const dcd_decode_args *args, float *dis, float *boxes);
+int dcd_dis_iou_accumulate(void *stream, const float *dis, int n_slots, const float *edges, int n_bins, int num_classes,
+                           const double *thresholds, double *table, int64_t *outside);
+
+/* ------------------------------------------------------------------------------------------------
  * Box NMS among the decoded candidates of every image of a batch, in ONE launch (csrc/nms.hip, arithmetic in csrc/nms_math.h):
  * TEST.USE_NMS.  The reference names the configuration keys and never reads them, so the rule is this library's:
  *   candidates  of image b: the prefix of its block of K rows whose raw score aux[., 0] is >= det_threshold (the raw scores
