@@ -2090,6 +2090,35 @@ DEPTH_STATS = 5                        # count, sum |e|, sum e, sum e^2, non-fin
 DEPTH_MAX_BINS = 16
 
 
+def _slot_args(who, names, vectors, ys, xs, classes, valid, image_table, extra):
+    """What the `*_estimates` wrappers check and convert alike: (B, M, C, vectors (B M, C), ys, xs, classes as float32, valid as
+    bytes, image_table).  extra: the caller's own per-slot tensor or None, checked only; names: the refusal's list of them."""
+    if vectors.dim() != 3:
+        raise ValueError("%s: vectors is %s, expected (B, M, C)" % (who, tuple(vectors.shape)))
+    B, M, C = vectors.shape
+    vec, table = _f32c(vectors).reshape(B * M, C), _f32c(image_table)
+    if tuple(table.shape) != (B, DECODE_TABLE):
+        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
+    if any(t is not None and t.numel() != B * M for t in (ys, xs, classes, valid, extra)):
+        raise ValueError("%s: %s hold one value per slot (%d x %d)" % (who, names, B, M))
+    return B, M, C, vec, _f32c(ys), _f32c(xs), _f32c(classes), _typed(valid, torch.uint8), table
+
+
+def _table_args(who, rows_name, rows, width, edges, table, outside, cell, tables_fn):
+    """What the `*_accumulate` wrappers check alike: rows (n, width), tables (class, bin) + cell -> (edges for C, n_bins, num_classes)."""
+    _lib.require_cuda(rows, table, outside)
+    edges = [float(e) for e in edges]
+    n_bins = len(edges) - 1
+    if rows.dim() != 2 or rows.shape[1] != width or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("%s: %s is %s %s, expected contiguous float32 (n, %d)" % (who, rows_name, rows.dtype, tuple(rows.shape), width))
+    num_classes = int(outside.shape[0]) if outside.dim() == 1 else -1
+    if (table.dtype != torch.float64 or outside.dtype != torch.int64 or not table.is_contiguous() or not outside.is_contiguous()
+            or tuple(table.shape) != (num_classes, n_bins) + cell):
+        raise ValueError("%s: table %s %s / outside %s %s do not fit %d bins (see %s)"
+                         % (who, table.dtype, tuple(table.shape), outside.dtype, tuple(outside.shape), n_bins, tables_fn))
+    return (_lib.c_float * max(len(edges), 1))(*edges), n_bins, num_classes
+
+
 def depth_estimates(vectors, ys, xs, classes, gt_z, valid, image_table, spec):
     """Every depth estimate of a batch of labelled objects in ONE launch: vectors (B, M, C) head outputs at the objects' cells,
     ys / xs / classes / gt_z / valid (B, M) (any numeric dtype; valid: 0 = empty slot), image_table (B, 16) as for
@@ -2097,17 +2126,9 @@ def depth_estimates(vectors, ys, xs, classes, gt_z, valid, image_table, spec):
     `DEPTH_METHODS`]; the `gmw` column is NaN (the caller's), an empty slot's row is all zeros.  No host synchronisation.
     A configuration the kernel does not cover gives `DcdHipError` (status 1) without a launch."""
     _lib.require_cuda(vectors, ys, xs, classes, gt_z, valid, image_table)
-    if vectors.dim() != 3:
-        raise ValueError("depth_estimates: vectors is %s, expected (B, M, C)" % (tuple(vectors.shape),))
-    B, M, C = vectors.shape
-    vec, table = _f32c(vectors).reshape(B * M, C), _f32c(image_table)
-    if tuple(table.shape) != (B, DECODE_TABLE):
-        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
-    per_slot = [ys, xs, classes, gt_z, valid]
-    if any(t.numel() != B * M for t in per_slot):
-        raise ValueError("depth_estimates: ys, xs, classes, gt_z and valid hold one value per slot (%d x %d)" % (B, M))
-    ys, xs, classes, gt_z = (_f32c(t) for t in per_slot[:4])
-    valid = _typed(valid, torch.uint8)
+    B, M, C, vec, ys, xs, classes, valid, table = _slot_args("depth_estimates", "ys, xs, classes, gt_z and valid", vectors, ys, xs,
+                                                             classes, valid, image_table, gt_z)
+    gt_z = _f32c(gt_z)
     a = decode_args(spec, B, M, C)
     est = torch.empty((B * M, DEPTH_ROW), dtype=torch.float32, device=vec.device)
     st = _lib.lib().dcd_depth_estimates(_lib.stream_of(vec), vec.data_ptr(), ys.data_ptr(), xs.data_ptr(), classes.data_ptr(),
@@ -2128,17 +2149,8 @@ def depth_accumulate(est, edges, table, outside):
     e = d - gt_z, in double, to the stats [count, sum |e|, sum e, sum e^2] of cell (c, i, method); a non-finite estimate raises the
     cell's fifth stat instead; an object in no bin counts in outside[c] only.  Every cell adds its objects in slot order, so the
     tables have the same bits however a split is cut into calls.  No host synchronisation."""
-    _lib.require_cuda(est, table, outside)
-    edges = [float(e) for e in edges]
-    n_bins = len(edges) - 1
-    if est.dim() != 2 or est.shape[1] != DEPTH_ROW or est.dtype != torch.float32 or not est.is_contiguous():
-        raise ValueError("depth_accumulate: est is %s %s, expected contiguous float32 (n, %d)" % (est.dtype, tuple(est.shape), DEPTH_ROW))
-    num_classes = int(outside.shape[0]) if outside.dim() == 1 else -1
-    if (table.dtype != torch.float64 or outside.dtype != torch.int64 or not table.is_contiguous() or not outside.is_contiguous()
-            or tuple(table.shape) != (num_classes, n_bins, len(DEPTH_METHODS), DEPTH_STATS)):
-        raise ValueError("depth_accumulate: table %s %s / outside %s %s do not fit %d bins (see depth_tables)"
-                         % (table.dtype, tuple(table.shape), outside.dtype, tuple(outside.shape), n_bins))
-    c_edges = (_lib.c_float * max(len(edges), 1))(*edges)
+    c_edges, n_bins, num_classes = _table_args("depth_accumulate", "est", est, DEPTH_ROW, edges, table, outside,
+                                               (len(DEPTH_METHODS), DEPTH_STATS), "depth_tables")
     st = _lib.lib().dcd_depth_accumulate(_lib.stream_of(est), est.data_ptr(), int(est.shape[0]), c_edges, n_bins, num_classes,
                                          table.data_ptr(), outside.data_ptr())
     _lib.check(st, "dcd_depth_accumulate")
@@ -2161,19 +2173,11 @@ def dis_iou_estimates(vectors, ys, xs, classes, gt, valid, image_table, spec, gm
     want_boxes=True returns (dis, boxes (B M, 16, 7)): h w l x y z ry of the label and of the fifteen variants.
     No host synchronisation.  A configuration the kernel does not cover gives `DcdHipError` (status 1) without a launch."""
     _lib.require_cuda(vectors, ys, xs, classes, gt, valid, image_table, gmw_z)
-    if vectors.dim() != 3:
-        raise ValueError("dis_iou_estimates: vectors is %s, expected (B, M, C)" % (tuple(vectors.shape),))
-    B, M, C = vectors.shape
-    vec, table = _f32c(vectors).reshape(B * M, C), _f32c(image_table)
-    if tuple(table.shape) != (B, DECODE_TABLE):
-        raise ValueError("image_table is %s, expected (%d, %d)" % (tuple(table.shape), B, DECODE_TABLE))
-    per_slot = [ys, xs, classes, valid] + ([] if gmw_z is None else [gmw_z])
-    if any(t.numel() != B * M for t in per_slot):
-        raise ValueError("dis_iou_estimates: ys, xs, classes, valid and gmw_z hold one value per slot (%d x %d)" % (B, M))
+    B, M, C, vec, ys, xs, classes, valid, table = _slot_args("dis_iou_estimates", "ys, xs, classes, valid and gmw_z", vectors, ys, xs,
+                                                             classes, valid, image_table, gmw_z)
     if gt.numel() != B * M * DIS_GT or gt.shape[-1] != DIS_GT:
         raise ValueError("dis_iou_estimates: gt is %s, expected (%d, %d, %d)" % (tuple(gt.shape), B, M, DIS_GT))
-    ys, xs, classes, gt = _f32c(ys), _f32c(xs), _f32c(classes), _f32c(gt)
-    valid = _typed(valid, torch.uint8)
+    gt = _f32c(gt)
     gmw_z = None if gmw_z is None else _f32c(gmw_z)
     a = decode_args(spec, B, M, C)
     dis = torch.empty((B * M, DIS_ROW), dtype=torch.float32, device=vec.device)
@@ -2198,21 +2202,12 @@ def dis_iou_accumulate(dis, edges, thresholds, table, outside):
     and the loose threshold, a hit is IoU > threshold; a non-finite overlap raises the cell's sixth stat instead; an object in no
     bin counts in outside[c] only.  Every cell adds its objects in slot order, so the tables have the same bits however a split is
     cut into calls.  No host synchronisation."""
-    _lib.require_cuda(dis, table, outside)
-    edges = [float(e) for e in edges]
-    n_bins = len(edges) - 1
-    if dis.dim() != 2 or dis.shape[1] != DIS_ROW or dis.dtype != torch.float32 or not dis.is_contiguous():
-        raise ValueError("dis_iou_accumulate: dis is %s %s, expected contiguous float32 (n, %d)" % (dis.dtype, tuple(dis.shape), DIS_ROW))
-    num_classes = int(outside.shape[0]) if outside.dim() == 1 else -1
-    if (table.dtype != torch.float64 or outside.dtype != torch.int64 or not table.is_contiguous() or not outside.is_contiguous()
-            or tuple(table.shape) != (num_classes, n_bins, len(DIS_VARIANTS), len(DIS_METRICS), DIS_STATS)):
-        raise ValueError("dis_iou_accumulate: table %s %s / outside %s %s do not fit %d bins (see dis_iou_tables)"
-                         % (table.dtype, tuple(table.shape), outside.dtype, tuple(outside.shape), n_bins))
+    c_edges, n_bins, num_classes = _table_args("dis_iou_accumulate", "dis", dis, DIS_ROW, edges, table, outside,
+                                               (len(DIS_VARIANTS), len(DIS_METRICS), DIS_STATS), "dis_iou_tables")
     flat = [float(t) for per_class in thresholds for per_metric in per_class for t in per_metric]
     if len(flat) != num_classes * len(DIS_METRICS) * 2:
         raise ValueError("dis_iou_accumulate: %d thresholds, expected (%d classes, %d metrics, strict and loose)"
                          % (len(flat), num_classes, len(DIS_METRICS)))
-    c_edges = (_lib.c_float * max(len(edges), 1))(*edges)
     c_thr = (_lib.c_double * len(flat))(*flat)
     st = _lib.lib().dcd_dis_iou_accumulate(_lib.stream_of(dis), dis.data_ptr(), int(dis.shape[0]), c_edges, n_bins, num_classes, c_thr,
                                            table.data_ptr(), outside.data_ptr())
