@@ -44,16 +44,11 @@ __device__ __forceinline__ f32x4 sw_fake_mfma(float a, float b, f32x4 c) { c.x =
 #else
 #define SW_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
 #endif
-constexpr int SW_PX = 16;                         // output pixels per row step
 constexpr int SW_WW = 24;                         // window columns
 constexpr int SW_RING = 9;                        // window rows
-constexpr int SW_CH = 16;                         // channels per wave
 constexpr int SW_CELLS = SW_RING * SW_WW;         // 216
 constexpr int SW_PLANE = SW_CELLS + 3;            // cells 216 .. 218: always-zero x / dummy gradient (invalid samples point here)
 constexpr int SW_ZERO = SW_CELLS;
-constexpr int SW_W_FLOATS = 9 * 16 * 64;          // prepared weights of one 16-channel chunk and one block of 64 outputs
-constexpr int SW_DW_FLOATS = 9 * 64 * SW_CH;      // grad_weight partial of one wave: [tap][o][c]
-constexpr int SW_PART_FLOATS = SW_DW_FLOATS + 64; // + the wave's grad_bias partial [o] (chunk 0 only)
 
 // Wp[ck][t][lane][s] = W[o = 4 s + (lane >> 4)][c = 16 ck + (lane & 15)][t], s < 16 nob (nob = blocks of 64 outputs): the lane's
 // B operands of the k-steps of a tap are 64 nob contiguous bytes -- four 16-byte loads per tap and output block instead of
@@ -1088,96 +1083,4 @@ __global__ __launch_bounds__(256) void dcn_sweep_epilogue(SweepEpilogueArgs a)
         sweep_reduce_dw_body(a.dwpart, a.gw, a.gbias, a.g, a.nck, a.nvp, a.far_scal, a.total_tiles, bid % a.dw_bx, a.dw_bx, bid / a.dw_bx, a.dw_by);
     else
         sweep_reduce_gemm_body(a.dwpart, a.gw, a.gemm_n, a.gemm_S, a.far_scal, a.total_tiles, bid, (int)gridDim.x - a.nb_coord - nb_bias);
-}
-
-struct SweepPlan {
-    int nck, nstrip, nseg, seg_rows, nv;
-    int nslot;                                    // persistent waves of the launch
-    int nob;                                      // blocks of 64 outputs (1, 2 or 4); > 1: grad_weight as one product from the col buffer
-    int dw_split, dw_kchunk;                      // nob > 1: pixel chunks of that product (per image), summed in a fixed order
-    size_t wp_floats, cpart_floats, dw_floats, col_floats;
-};
-constexpr int SW_GEMM_T = 128, SW_GEMM_K = 16;    // sgemm_f32.inc's tile edge and k step (checked where the product is launched)
-
-__host__ inline SweepPlan sweep_plan(const Geom &g)
-{
-    SweepPlan p;
-    p.nck = (g.C + SW_CH - 1) / SW_CH;
-    p.nstrip = (g.W + SW_PX - 1) / SW_PX;
-    // segments: a unit (one wave's sweep over its rows of a strip) pays ~5 rows' worth of ring warm-up and row retirement on top
-    // of its rows, and the launch runs ceil(units / 1024 resident waves) units deep: the segment count with the least
-    // (depth x (rows + 5)).  Rounds 3-4 kept segments at >= 8 rows, which left the one-image step's <= 48x160 layers at a
-    // quarter to a half of the wave slots (one image, 128->64 @ 48x160: 0.155 -> 0.120 ms; 256->128 @ 24x80 0.162 -> 0.111).
-    const int64_t base = (int64_t)g.B * p.nstrip * p.nck;
-    static const int min_rows = dcd_env("DCD_SWEEP_MIN_ROWS") && atoi(dcd_env("DCD_SWEEP_MIN_ROWS")) > 0 ? atoi(dcd_env("DCD_SWEEP_MIN_ROWS")) : 3;
-    int best = 1;
-    int64_t best_cost = -1;
-    for (int ns = 1; ns <= g.H; ++ns) {
-        const int rows = (g.H + ns - 1) / ns;
-        if (rows < min_rows && ns > 1) break;
-        const int real_ns = (g.H + rows - 1) / rows;
-        const int64_t total = base * real_ns;
-        const int64_t cost = ((total + 1023) / 1024) * (rows + 5);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = real_ns; }
-    }
-    p.seg_rows = (g.H + best - 1) / best;
-    p.nseg = (g.H + p.seg_rows - 1) / p.seg_rows;
-    p.nv = g.B * p.nstrip * p.nseg;
-    // persistent waves: about one round of the 1024 wave slots (4 per CU), in whole groups of 8 * nck (a wave keeps its chunk);
-    // SW_WAVES divides 8, so whole workgroups too
-    const int64_t units = (int64_t)((p.nv + 7) / 8) * 8 * p.nck;
-    const int grp = 8 * p.nck;
-    int64_t slots = units < 1024 ? units : (1024 / grp) * (int64_t)grp;
-    if (slots < grp) slots = grp;
-    if (const char *e = dcd_env("DCD_SWEEP_SLOTS")) {             // A/B: 0 = one unit per wave
-        const int64_t v_ = atoll(e);
-        slots = v_ <= 0 ? units : (v_ / grp > 0 ? v_ / grp : 1) * grp;
-    }
-    if (slots > units) slots = units;
-    p.nslot = (int)slots;
-    p.nob = g.Co <= 64 ? 1 : (g.Co <= 128 ? 2 : 4);
-    p.wp_floats = (size_t)p.nck * SW_W_FLOATS * p.nob;
-    p.cpart_floats = (size_t)p.nck * g.B * 27 * g.HoWo;
-    p.dw_split = 1;
-    p.dw_kchunk = 0;
-    if (p.nob == 1) {
-        p.dw_floats = (size_t)p.nslot * SW_PART_FLOATS;
-        p.col_floats = 0;
-    } else {
-        // grad_weight[o][c * 9 + t] = sum_b sum_p dY[b][o][p] col[b][c * 9 + t][p]: per image Co x 9C tiles of 128 x 128, the pixel
-        // axis cut so that the launch has ~512 workgroups (chunks of at least 256 pixels)
-        const int K9 = g.C * 9;
-        const int tiles = ((g.Co + SW_GEMM_T - 1) / SW_GEMM_T) * ((K9 + SW_GEMM_T - 1) / SW_GEMM_T) * g.B;
-        int sp = (512 + tiles - 1) / tiles;
-        const int smax = g.HoWo / 256 > 1 ? g.HoWo / 256 : 1;
-        if (sp > smax) sp = smax;
-        if (sp < 1) sp = 1;
-        p.dw_kchunk = ((g.HoWo + sp - 1) / sp + SW_GEMM_K - 1) / SW_GEMM_K * SW_GEMM_K;
-        p.dw_split = (g.HoWo + p.dw_kchunk - 1) / p.dw_kchunk;
-        p.col_floats = (size_t)g.B * K9 * g.HoWo;
-        p.dw_floats = (size_t)g.B * p.dw_split * g.Co * K9;
-    }
-    return p;
-}
-
-// DCD_BWD_SWEEP (read per call: the tests switch it inside one process): 0 restores the three-pass backward, 2 leaves the
-// layers the dense path takes (Cin >= 256) to it
-__host__ inline int sweep_mode()
-{
-    const char *e = dcd_env("DCD_BWD_SWEEP");
-    return !e ? 1 : (atoi(e) == 0 ? 0 : (atoi(e) == 2 ? 2 : 1));
-}
-
-__host__ inline bool sweep_ok(const Geom &g)
-{
-    return sweep_mode() != 0 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.dh == 1 && g.dw == 1 && g.dg == 1 &&
-           (g.W & 3) == 0 && g.H >= 8 && g.W >= 32 && g.Co <= 256 && ((int64_t)g.HoWo * 27 & 3) == 0 &&
-           (g.Co <= 64 || (((int64_t)g.C * 9 * g.HoWo < (1ll << 29)) && (int64_t)g.B * g.C * 9 * g.HoWo * 4 <= (1ll << 31)));
-}
-
-__host__ inline size_t sweep_workspace_bytes(const Geom &g)
-{
-    if (!sweep_ok(g)) return 0;
-    const SweepPlan p = sweep_plan(g);
-    return ((p.wp_floats + p.cpart_floats + p.dw_floats + p.col_floats) * sizeof(float) + 255) / 256 * 256 + 256;
 }

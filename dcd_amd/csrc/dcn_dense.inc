@@ -266,66 +266,6 @@ __global__ void dcn_dense_reduce(const float *__restrict__ part, float *__restri
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// DCD_DCN_DENSE: unset = wide inputs only (Cin >= 256); 0 = never; 1 = every geometry the alignment rules allow (tests).
-inline int dense_mode()
-{
-    const char *e = dcd_env("DCD_DCN_DENSE");                  // read per call: the tests switch it inside one process
-    return !e ? 2 : (atoi(e) == 1 ? 1 : (atoi(e) == 0 ? 0 : 2));
-}
-
-// column buffer [B][C*KK][HoWo]; the backward's Tt [B][HoWo][Kp] (Kp >= C*KK: channels padded to 32 per group) shares it
-inline size_t dense_col_floats(const Geom &g) { return (size_t)g.B * g.Kp * g.HoWo; }
-
-// backward = true: the gradient pass; it pays off earlier than the forward (the fused backward needs three kernels with the
-// product inside, the dense one shares T between grad_input and the coordinate gradients): measured on 128->128 @ 48x160
-// forward 0.35 (dense) vs 0.22 ms (fused), backward 1.20 vs 1.45 ms.
-inline bool dense_ok(const Geom &g, bool backward)
-{
-    const int mode = dense_mode();
-    if (mode == 0) return false;
-    const int64_t K9 = (int64_t)g.C * g.KK;
-    if ((g.HoWo & 3) || (K9 & 3) || (g.cpg % 16) || g.W < 2 || (int64_t)g.Kp * g.HoWo >= (1ll << 30) ||
-        (int64_t)g.Co * g.Kp >= (1ll << 31))
-        return false;
-    if (dense_col_floats(g) * sizeof(float) > ((size_t)1 << 30)) return false;
-    if (mode == 1 || g.C >= 256) return true;
-    return backward && g.C >= 128 && g.Co >= 128;
-}
-
-struct DensePlan { int fwd_split, fwd_kchunk, dw_split, dw_kchunk; size_t part_floats; };
-
-inline DensePlan dense_plan(const Geom &g)
-{
-    DensePlan p;
-    const int K9 = g.C * g.KK;
-    const int mt = (g.Co + SG_T - 1) / SG_T;
-    auto pick = [](int tiles, int K, int min_chunk) {
-        int s = (512 + tiles - 1) / tiles;
-        const int smax = K / min_chunk > 1 ? K / min_chunk : 1;
-        if (s > smax) s = smax;
-        if (s < 1) s = 1;
-        return s;
-    };
-    const int ft = mt * ((g.HoWo + SG_T - 1) / SG_T) * g.B;
-    p.fwd_split = pick(ft, K9, 512);
-    p.fwd_kchunk = ((K9 + p.fwd_split - 1) / p.fwd_split + SG_K - 1) / SG_K * SG_K;
-    p.fwd_split = (K9 + p.fwd_kchunk - 1) / p.fwd_kchunk;
-    const int wt = mt * ((K9 + SG_T - 1) / SG_T) * g.B;
-    p.dw_split = pick(wt, g.HoWo, 256);
-    p.dw_kchunk = ((g.HoWo + p.dw_split - 1) / p.dw_split + SG_K - 1) / SG_K * SG_K;
-    p.dw_split = (g.HoWo + p.dw_kchunk - 1) / p.dw_kchunk;
-    const size_t fp = p.fwd_split > 1 ? (size_t)g.B * p.fwd_split * g.Co * g.HoWo : 0;
-    const size_t wp = (size_t)g.B * p.dw_split * g.Co * K9;
-    p.part_floats = fp > wp ? fp : wp;
-    return p;
-}
-
-inline size_t dense_workspace_bytes(const Geom &g)
-{
-    if (!dense_ok(g, true)) return 0;
-    return 256 + (dense_col_floats(g) + dense_plan(g).part_floats) * sizeof(float);
-}
-
 inline void dense_im2col(hipStream_t stream, const float *input, const float *offset, const float *mask, float *col, const Geom &g)
 {
     hipLaunchKernelGGL(dcn_dense_im2col, dim3((g.HoWo + 63) / 64, g.dg * g.KK, g.B), dim3(256), 0, stream, input, offset, mask, col, g);
@@ -341,11 +281,11 @@ inline void dense_gemm(hipStream_t stream, int prec, bool ak, bool bk, const Sge
 }
 
 inline void dense_forward(hipStream_t stream, const float *input, const float *weight, const float *bias, const float *offset,
-                          const float *mask, float *output, const Geom &g, float *col, int split)
+                          const float *mask, float *output, const Geom &g, const DcnWorkspace &m, void *workspace, int split)
 {
-    const DensePlan p = dense_plan(g);
+    const DensePlan &p = m.dense;
     const int K9 = g.C * g.KK;
-    float *part = col + dense_col_floats(g);
+    float *col = m.dense_col.in<float>(workspace), *part = m.dense_part.in<float>(workspace);
     dense_im2col(stream, input, offset, mask, col, g);
     SgemmArgs a;
     a.A = weight; a.B = col; a.M = g.Co; a.N = g.HoWo; a.K = K9; a.lda = K9; a.ldb = g.HoWo; a.ldc = g.HoWo;
@@ -366,11 +306,11 @@ inline void dense_forward(hipStream_t stream, const float *input, const float *w
 // after: dcn_prep_weights (Wb), zero_ranges (grad_bias), dcn_offset_absmax, dcn_build_inverse (unpacked lists)
 inline void dense_backward(hipStream_t stream, const float *input, const float *wb, const float *offset, const float *mask,
                            const float *grad_output, float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight,
-                           const Geom &g, const InvLists &inv, float *col, int split)
+                           const Geom &g, const InvLists &inv, const DcnWorkspace &m, void *workspace, int split)
 {
-    const DensePlan p = dense_plan(g);
+    const DensePlan &p = m.dense;
     const int K9 = g.C * g.KK, HW = g.H * g.W;
-    float *part = col + dense_col_floats(g);
+    float *col = m.dense_col.in<float>(workspace), *part = m.dense_part.in<float>(workspace);
     SgemmArgs a;
     // Tt[b][p][kp] = sum_o Wb[o][kp] dY[b][o][p]
     a.A = wb; a.B = grad_output; a.C = col; a.bias = nullptr; a.M = g.Kp; a.N = g.HoWo; a.K = g.Co;

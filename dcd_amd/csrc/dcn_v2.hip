@@ -40,6 +40,7 @@
 #include "../../include/dcd_hip.h"
 #include "tuning_env.h"
 #include "lds_limit.h"
+#include "dcn_workspace.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x32 __attribute__((ext_vector_type(32)));
@@ -49,37 +50,6 @@ namespace {
 template <int N> struct IntC {
     static constexpr int value = N;
 };
-
-struct Geom {
-    int B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg;
-    int Ho, Wo, HoWo, KK, cpg, cpgp, Kp, Cop;  // cpgp: channels/group padded to 32; Kp = dg*KK*cpgp; Cop: Co padded to 32
-};
-
-__host__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-__host__ inline bool make_geom(Geom &g, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph,
-                               int pw, int dh, int dw, int dg)
-{
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Co <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 ||
-        pw < 0 || dh <= 0 || dw <= 0 || dg <= 0 || C % dg)
-        return false;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.Co = Co; g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw;
-    g.ph = ph; g.pw = pw; g.dh = dh; g.dw = dw; g.dg = dg;
-    g.Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1;
-    g.Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
-    if (g.Ho <= 0 || g.Wo <= 0) return false;
-    g.HoWo = g.Ho * g.Wo;
-    g.KK = kh * kw;
-    g.cpg = C / dg;
-    g.cpgp = round_up(g.cpg, 32);
-    g.Kp = dg * g.KK * g.cpgp;
-    g.Cop = round_up(Co, 32);
-    // 32-bit index safety for per-image planes
-    if ((int64_t)C * H * W >= (1ll << 31) || (int64_t)Co * g.HoWo >= (1ll << 31) ||
-        (int64_t)g.Kp * g.Cop >= (1ll << 31) || (int64_t)dg * 2 * g.KK * g.HoWo >= (1ll << 31))
-        return false;
-    return true;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Weight re-layout: W[o][c][t] -> Wf[k'][Cop], Wb[Cop][Kp], zero padded.
@@ -342,9 +312,6 @@ __global__ __launch_bounds__(256) void dcn_fwd_f32(const float *__restrict__ in,
 
 // ---- constants of the workgroup-tiled forward (defined here: the rescue mode of dcn_fwd9_f32 reads its weight layout)
 constexpr int TL_WW = 40;                   // window cols  c0-4 .. c0+35 (16-byte aligned rows)
-constexpr int TL_CH = 8;                    // channels per chunk
-constexpr int TL_OB = 64;                   // output channels per workgroup (two 32-wide MFMA blocks)
-constexpr int TL_W_FLOATS = 9 * TL_OB * TL_CH;            // 4608: [tap][o][h][4 steps]
 constexpr int TL_NW = TL_W_FLOATS / 4;                    // 1152 dwordx4 per chunk (weights)
 // TR = waves per workgroup = tile rows (8: 16-row window, 1 workgroup / CU; 4: 12-row window, 2 workgroups / CU)
 template <int TR> struct TileCfg {
@@ -943,7 +910,6 @@ static bool forward_keeps_far_samples(const void *weight, int64_t ncoord)
     return far != HANDOVER_UNKNOWN && (int64_t)far * 64 <= ncoord;
 }
 
-constexpr int INV_CAP = 10;     // list capacity per (cell, tap): offsets below 1 px give at most 9, typically 4
 constexpr int INV_RCAP = 8;     // offsets up to this many pixels are inverted; beyond -> atomic fallback
 constexpr int INV_RTILE = 3;    // the tiled grad_input kernel's dY window covers lists built with a radius up to this
 constexpr int INV_OVERFLOW = 255;
@@ -2050,7 +2016,6 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_f32(const float *__restric
 constexpr int DW_TR = 2;
 constexpr int DW_WH = DW_TR + 8;                      // 10 window rows
 constexpr int DW_PLANE = DW_WH * TL_WW + 2;           // 402 = 2 * 201
-constexpr int DW_CB = 32;                             // channels per block
 constexpr int DW_IN_FLOATS = DW_CB * DW_PLANE;        // 12 864
 constexpr int DW_DYS = DW_TR * 32 + 1;                // dY row stride 65
 constexpr int DW_DY_FLOATS = TL_OB * DW_DYS;          // 4 160
@@ -2372,439 +2337,512 @@ __global__ void dcn_offset_mask_merge(const float *__restrict__ goff, const floa
 
 #include "dcn_dense.inc"
 
-extern "C" {
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+// One call's arguments, geometry and workspace map (dcn_workspace.h); then one launcher per kernel family -- it owns the instance
+// choice, grid, block, LDS bytes and LDS-limit raise, what differs between its call sites is a parameter -- then the routes, and
+// the two entry points: validate, map, route, call.
+namespace {
 
-// partial grad_weight blocks of the tiled kernel: (channel blocks x output slices x pixel splits) x [64 o][32 c][9]
-static size_t dw_partial_floats(int Cin, int Cout)
-{
-    const size_t nb = (size_t)((Cin + DW_CB - 1) / DW_CB) * ((Cout + TL_OB - 1) / TL_OB);
-    return (nb > 512 ? nb : 512) * (size_t)(2 * 32 * DW_CB * 9);
-}
-
-// per (image, tap segment, 8x8 block of output pixels) one byte, after the grad_weight partials
-static size_t tileflag_bytes(const Geom &g) { return ((size_t)g.B * ((g.H + 3) / 4) * ((g.W + 31) / 32) + 255) / 256 * 256; }
-
-// [block maxima | tile flags of the tiled grad_input kernel]
-static size_t blockmax_bytes(const Geom &g)
-{
-    return ((size_t)g.B * g.dg * g.KK * ((g.Ho + 7) / 8) * ((g.Wo + 7) / 8) + 255) / 256 * 256 + tileflag_bytes(g);
-}
-
-static size_t base_workspace_bytes(const Geom &g)
-{
-    // [Wf | Wb | scalars (256 B) | inverse lists: cnt, idx, w | far-tile flags | far-tile list | grad_weight partials]
-    const size_t cells = (size_t)g.B * g.dg * g.KK * g.H * g.W;
-    const size_t ntile = (size_t)g.B * ((g.HoWo + 31) / 32);
-    const size_t n = (size_t)g.Kp * g.Cop * sizeof(float) * 2 + 256 + ((cells + 255) / 256 * 256) + cells * INV_CAP * 8 + 256 +
-                     ((ntile + 255) / 256 * 256) + (ntile + 63) / 64 * 64 * sizeof(int) + dw_partial_floats(g.C, g.Co) * sizeof(float);
-    return (n + 255) / 256 * 256 + blockmax_bytes(g);
-}
-
-size_t dcd_dcn_v2_workspace_bytes(int B, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
-                                  int pw, int dh, int dw, int dg)
-{
+struct DcnCall {
+    hipStream_t stream;
+    const float *input, *weight, *bias, *offset, *mask;
+    float *output = nullptr;                                   // forward
+    const float *grad_output = nullptr;                        // backward
+    float *grad_input = nullptr, *grad_offset = nullptr, *grad_mask = nullptr, *grad_weight = nullptr, *grad_bias = nullptr;
     Geom g;
-    if (!make_geom(g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return 0;
-    // dense path (dcn_dense.inc): [column buffer | split-K partials] after the lists; then the one-pass backward's
-    // [prepared weights | grad_offset / grad_mask partial planes | grad_weight partials] (dcn_bwd_sweep.inc)
-    return base_workspace_bytes(g) + dense_workspace_bytes(g) + sweep_workspace_bytes(g);
+    int precision;
+    bool split, one;              // not DCD_PREC_F32 (the generic kernels: DCD_PREC_BF16 runs their split form); DCD_PREC_BF16
+    void *ws;
+    DcnWorkspace m;
+    // backward: the first bracket of the map as pointers
+    float *wf, *wb;
+    unsigned *absmax;             // scalars: max |offset| bits, far-tile count, overflowed-list count, far-coordinate count
+    unsigned char *far_flag, *blockmax, *tileflag;
+    int *far_list;
+    InvLists inv;                 // packed = 0, tileflag = null: the routes set what they use
+};
+
+inline int launch_status() { return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH; }
+// blocks of a 256-thread grid-stride loop over n items, at most cap
+inline unsigned stride_blocks(size_t n, unsigned cap) { return (unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
+// blocks of an offset scan over n coordinates (16 per thread), at most 512
+inline int scan_blocks(int64_t n)
+{
+    const int b = (int)((n + 4095) / 4096);
+    return b > 512 ? 512 : b;
+}
+inline void zero_range(ZeroRanges &z, int slot, void *p, size_t dwords) { z.p[slot] = (unsigned *)p; z.n[slot] = (unsigned)dwords; }
+
+void launch_prep_weights(const DcnCall &c, float *wf, float *wb)
+{
+    hipLaunchKernelGGL(dcn_prep_weights, dim3(stride_blocks((size_t)c.g.Kp * c.g.Cop, 2048)), dim3(256), 0, c.stream, c.weight, wf, wb,
+                       c.g);
 }
 
-int dcd_dcn_v2_forward(void *stream_, const float *input, const float *weight, const float *bias,
-                       const float *offset, const float *mask, float *output, int B, int Cin, int H, int W,
-                       int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg,
-                       int precision, void *workspace, size_t workspace_bytes)
+// also zeroes the region flags and the far counter behind them, and lays out the rescue pass's weights
+void launch_prep_weights_tile(const DcnCall &c, float *wl, unsigned *flags, float *wf9)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    Geom g;
-    if (!input || !weight || !bias || !offset || !mask || !output || !workspace) return DCD_ERR_BAD_ARG;
-    if (!make_geom(g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return DCD_ERR_BAD_ARG;
-    // DCD_PREC_BF16X3 permits (does not oblige) the split-bf16 contraction: the workgroup-tiled kernels have it, every other
-    // geometry runs the exact fp32 kernels, which are inside any tolerance the split form is
-    // DCD_PREC_BF16 (one product of bf16-rounded operands): the same kernels and prepared weights, their low halves unread
-    if (precision != DCD_PREC_F32 && precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
-    const bool split = precision != DCD_PREC_F32;
-    const bool one = precision == DCD_PREC_BF16;
-    const size_t nw = (size_t)g.Kp * g.Cop;
-    if (workspace_bytes < nw * sizeof(float) * 2) return DCD_ERR_WORKSPACE;
-    if (dense_ok(g, false)) {                                  // wide input, small map: column buffer + GEMM
-        if (workspace_bytes < base_workspace_bytes(g) + dense_workspace_bytes(g)) return DCD_ERR_WORKSPACE;
-        dense_forward(stream, input, weight, bias, offset, mask, output, g, (float *)((char *)workspace + base_workspace_bytes(g)),
-                      precision);
-        return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-    }
-    float *wf = (float *)workspace, *wb = wf + nw;
+    const FwdTilePlan &t = c.m.tile;
+    const dim3 grid(stride_blocks(t.nwl, 2048));
+    if (c.split)
+        hipLaunchKernelGGL(dcn_prep_weights_tile_bf16, grid, dim3(256), 0, c.stream, c.weight, (unsigned short *)wl, c.g, t.nchunk, t.nz,
+                           flags, t.nflag_words, wf9);
+    else
+        hipLaunchKernelGGL(dcn_prep_weights_tile, grid, dim3(256), 0, c.stream, c.weight, wl, c.g, t.nchunk, t.nz, flags, t.nflag_words, wf9);
+}
 
-    const int tiles = (g.HoWo + 31) / 32;
-    const int nb = g.Cop / 32;
-    const int mb = pick_mb(nb, tiles * B);
-    dim3 grid((tiles + 3) / 4, B, (nb + mb - 1) / mb), block(256);
-#ifndef DCN_NO_FWD_TILE
-    // workgroup-tiled LDS kernel: the DLA-34 shape (3x3, stride 1, pad 1, dil 1, dg 1); maps of at least 16 rows
-    if (kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && dg == 1 && (W & 3) == 0 &&
-        H >= 8 && W >= 32 && dcd_env("DCD_NO_TILE") == nullptr) {
-        const int nz = (Cout + TL_OB - 1) / TL_OB;
-        const int nchunk = split ? (Cin + TB_CH - 1) / TB_CH : (Cin + TL_CH - 1) / TL_CH;
-        const size_t nwl = (size_t)nz * nchunk * (split ? TB_W_FLOATS : TL_W_FLOATS);
-        if (nwl <= 2 * nw) {                                          // Wl lives in the [Wf | Wb] area
-            static LdsLimit lds_limit8, lds_limit4, lds_limit8b, lds_limit4b;
-            static int tile_rows = 0;
-            if (tile_rows == 0) {
-                const char *e = dcd_env("DCD_TILE_ROWS");
-                tile_rows = (e && atoi(e) == 4) ? 4 : 8;
-            }
-            if (!lds_limit8.raise((int)(2 * TileCfg<8>::BUF * sizeof(float)), dcn_fwd_tile_f32<8>) ||
-                !lds_limit4.raise((int)(2 * TileCfg<4>::BUF * sizeof(float)), dcn_fwd_tile_f32<4>))
-                return DCD_ERR_LAUNCH;
-            if (split && (!lds_limit8b.raise((int)(TileCfgB<8>::NBUF * TileCfgB<8>::BUF * sizeof(float)), dcn_fwd_tile_bf16x3<8, 3>,
-                                             dcn_fwd_tile_bf16x3<8, 1>) ||
-                          !lds_limit4b.raise((int)(TileCfgB<4>::NBUF * TileCfgB<4>::BUF * sizeof(float)), dcn_fwd_tile_bf16x3<4, 3>,
-                                             dcn_fwd_tile_bf16x3<4, 1>)))
-                return DCD_ERR_LAUNCH;
-            static int rescue_taps = 0;
-            if (rescue_taps == 0) {
-                const char *e = dcd_env("DCD_FWD_RESCUE_TAPS");       // A/B: far taps in the worst wave that hand a region to the rescue kernel
-                rescue_taps = (e && atoi(e) >= 1 && atoi(e) <= 10) ? atoi(e) : 5;
-            }
-            const int tiles_x = (g.Wo + 31) / 32;
-            const bool rows8 = tile_rows == 8 && (int64_t)tiles_x * ((g.Ho + 7) / 8) * B * nz >= 512;
-            const int TRr = rows8 ? 8 : 4;
-            const int regions = tiles_x * ((g.Ho + TRr - 1) / TRr);
-            // region flags ("far samples dominate here: left to the rescue pass") live behind the weight area
-            const int nflag_words = (B * regions + 3) / 4 + 1;        // + the far-coordinate counter, zeroed with the flags
-            unsigned char *flags = (unsigned char *)(wf + 2 * nw);
-            unsigned *far_count = (unsigned *)flags + (nflag_words - 1);
-            const int64_t ncoord = (int64_t)B * 18 * g.HoWo;
-            const bool keeps = forward_keeps_far_samples(weight, ncoord);     // no far count, no rescue launch (policy above)
-            const unsigned far_limit = keeps ? 0xffffffffu : (unsigned)(ncoord / 32 < 0xffffffffll ? ncoord / 32 : 0xffffffffll);
-            const int rescue_taps_call = keeps ? 10 : rescue_taps;            // 10: no region is ever handed over (nine taps)
-            const size_t n9 = (size_t)Cin * 9 * g.Cop;
-            if (nwl <= nw && n9 <= nw && workspace_bytes >= 2 * nw * sizeof(float) + (size_t)nflag_words * 4) {
-                float *wf9 = wf + nw;                         // [Wl | Wf9 | flags]
-                if (split)
-                    hipLaunchKernelGGL(dcn_prep_weights_tile_bf16, dim3((unsigned)((nwl + 255) / 256 < 2048 ? (nwl + 255) / 256 : 2048)),
-                                       dim3(256), 0, stream, weight, (unsigned short *)wf, g, nchunk, nz, (unsigned *)flags, nflag_words, wf9);
-                else
-                    hipLaunchKernelGGL(dcn_prep_weights_tile, dim3((unsigned)((nwl + 255) / 256 < 2048 ? (nwl + 255) / 256 : 2048)),
-                                       dim3(256), 0, stream, weight, wf, g, nchunk, nz, (unsigned *)flags, nflag_words, wf9);
-                if (!keeps) {
-                    int gsz = (int)((ncoord + 4095) / 4096);
-                    if (gsz > 512) gsz = 512;
-                    hipLaunchKernelGGL(dcn_fwd_far_count, dim3(gsz), dim3(256), 0, stream, offset, ncoord, far_count);
-                }
-#define DCD_FWD_TILE_B(TRV, NPV)                                                                                                      \
-    hipLaunchKernelGGL((dcn_fwd_tile_bf16x3<TRV, NPV>), dim3(regions, B, nz), dim3(TRV * 64),                                         \
-                       TileCfgB<TRV>::NBUF * TileCfgB<TRV>::BUF * sizeof(float), stream, input, offset, mask, (const float *)wf, bias, \
-                       output, g, tiles_x, nchunk, flags, (const float *)wf9, rescue_taps_call, (const unsigned *)far_count, far_limit)
-                if (split && rows8) {
-                    if (one) DCD_FWD_TILE_B(8, 1); else DCD_FWD_TILE_B(8, 3);
-                } else if (split) {
-                    if (one) DCD_FWD_TILE_B(4, 1); else DCD_FWD_TILE_B(4, 3);
-                }
-#undef DCD_FWD_TILE_B
-                else if (rows8)
-                    hipLaunchKernelGGL(dcn_fwd_tile_f32<8>, dim3(regions, B, nz), dim3(512), 2 * TileCfg<8>::BUF * sizeof(float), stream,
-                                       input, offset, mask, wf, bias, output, g, tiles_x, nchunk, flags, (const float *)wf9, rescue_taps_call,
-                                       (const unsigned *)far_count, far_limit);
-                else
-                    hipLaunchKernelGGL(dcn_fwd_tile_f32<4>, dim3(regions, B, nz), dim3(256), 2 * TileCfg<4>::BUF * sizeof(float), stream,
-                                       input, offset, mask, wf, bias, output, g, tiles_x, nchunk, flags, (const float *)wf9, rescue_taps_call,
-                                       (const unsigned *)far_count, far_limit);
-                if (keeps) return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-                // rescue pass: register-gather kernel over the flagged regions only (usually none: its waves exit at once)
-                const int nb9 = g.Cop / 32, mb9 = nb9 >= 4 ? 4 : nb9 >= 2 ? 2 : 1;
-                dim3 gridr((tiles_x * g.Ho + 3) / 4, B, (nb9 + mb9 - 1) / mb9);
-                if (mb9 == 4)
-                    hipLaunchKernelGGL((dcn_fwd9_f32<4, true>), gridr, dim3(256), 0, stream, input, offset, mask, wf9, bias, output, g,
-                                       (const unsigned char *)flags, tiles_x, TRr, nchunk);
-                else if (mb9 == 2)
-                    hipLaunchKernelGGL((dcn_fwd9_f32<2, true>), gridr, dim3(256), 0, stream, input, offset, mask, wf9, bias, output, g,
-                                       (const unsigned char *)flags, tiles_x, TRr, nchunk);
-                else
-                    hipLaunchKernelGGL((dcn_fwd9_f32<1, true>), gridr, dim3(256), 0, stream, input, offset, mask, wf9, bias, output, g,
-                                       (const unsigned char *)flags, tiles_x, TRr, nchunk);
-                return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-            }
-        }
+// false: a kernel's dynamic-LDS limit could not be raised
+bool launch_fwd_tile(const DcnCall &c, const float *wl, unsigned char *flags, const float *wf9, int rescue_taps,
+                     const unsigned *far_count, unsigned far_limit)
+{
+    static LdsLimit lds_limit8, lds_limit4, lds_limit8b, lds_limit4b;
+    if (!lds_limit8.raise((int)(2 * TileCfg<8>::BUF * sizeof(float)), dcn_fwd_tile_f32<8>) ||
+        !lds_limit4.raise((int)(2 * TileCfg<4>::BUF * sizeof(float)), dcn_fwd_tile_f32<4>))
+        return false;
+    if (c.split && (!lds_limit8b.raise((int)(TileCfgB<8>::NBUF * TileCfgB<8>::BUF * sizeof(float)), dcn_fwd_tile_bf16x3<8, 3>,
+                                       dcn_fwd_tile_bf16x3<8, 1>) ||
+                    !lds_limit4b.raise((int)(TileCfgB<4>::NBUF * TileCfgB<4>::BUF * sizeof(float)), dcn_fwd_tile_bf16x3<4, 3>,
+                                       dcn_fwd_tile_bf16x3<4, 1>)))
+        return false;
+    const FwdTilePlan &t = c.m.tile;
+    auto go = [&](auto kernel, size_t lds_floats) {
+        hipLaunchKernelGGL(kernel, dim3(t.regions, c.g.B, t.nz), dim3(t.rows * 64), lds_floats * sizeof(float), c.stream, c.input, c.offset,
+                           c.mask, wl, c.bias, c.output, c.g, t.tiles_x, t.nchunk, flags, wf9, rescue_taps, far_count, far_limit);
+    };
+    if (c.split && t.rows == 8) {
+        if (c.one) go(dcn_fwd_tile_bf16x3<8, 1>, TileCfgB<8>::NBUF * TileCfgB<8>::BUF);
+        else go(dcn_fwd_tile_bf16x3<8, 3>, TileCfgB<8>::NBUF * TileCfgB<8>::BUF);
+    } else if (c.split) {
+        if (c.one) go(dcn_fwd_tile_bf16x3<4, 1>, TileCfgB<4>::NBUF * TileCfgB<4>::BUF);
+        else go(dcn_fwd_tile_bf16x3<4, 3>, TileCfgB<4>::NBUF * TileCfgB<4>::BUF);
+    } else if (t.rows == 8) {
+        go(dcn_fwd_tile_f32<8>, 2 * TileCfg<8>::BUF);
+    } else {
+        go(dcn_fwd_tile_f32<4>, 2 * TileCfg<4>::BUF);
     }
-#endif
-#ifndef DCN_NO_FWD9
-    if (g.KK == 9 && W >= 2 && (size_t)Cin * 9 * g.Cop <= nw) {      // 3x3 fast path (the only shape DGDE uses); reuses the Wf area
-        const size_t n9 = (size_t)Cin * 9 * g.Cop;
-        hipLaunchKernelGGL(dcn_prep_weights9, dim3((unsigned)((n9 + 255) / 256 < 2048 ? (n9 + 255) / 256 : 2048)), dim3(256), 0,
-                           stream, weight, wf, g);
-        const int mb9 = mb > 4 ? 4 : mb;                   // 72 VGPRs of tap state: keep <= 64 accumulator registers
-        dim3 grid9((tiles + 3) / 4, B, (nb + mb9 - 1) / mb9);
-        switch (mb9) {
-            case 4: hipLaunchKernelGGL(dcn_fwd9_f32<4>, grid9, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-            case 2: hipLaunchKernelGGL(dcn_fwd9_f32<2>, grid9, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-            default: hipLaunchKernelGGL(dcn_fwd9_f32<1>, grid9, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-        }
-        return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return true;
+}
+
+// the 3x3 register-gather kernel, mb9 (4, 2 or 1) output blocks per wave over gx workgroups per image; flags != null: as the
+// tiled kernel's rescue pass, over the flagged regions only
+void launch_fwd9(const DcnCall &c, const float *w9, int mb9, int gx, const unsigned char *flags = nullptr, int tiles_x = 0, int rows = 0,
+                 int nchunk = 0)
+{
+    const dim3 grid(gx, c.g.B, (c.g.Cop / 32 + mb9 - 1) / mb9);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.stream, c.input, c.offset, c.mask, w9, c.bias, c.output, c.g, flags, tiles_x, rows,
+                           nchunk);
+    };
+    if (flags) {
+        if (mb9 == 4) go(dcn_fwd9_f32<4, true>);
+        else if (mb9 == 2) go(dcn_fwd9_f32<2, true>);
+        else go(dcn_fwd9_f32<1, true>);
+    } else {
+        if (mb9 == 4) go(dcn_fwd9_f32<4, false>);
+        else if (mb9 == 2) go(dcn_fwd9_f32<2, false>);
+        else go(dcn_fwd9_f32<1, false>);
     }
-#endif
-    hipLaunchKernelGGL(dcn_prep_weights, dim3((unsigned)((nw + 255) / 256 < 2048 ? (nw + 255) / 256 : 2048)), dim3(256),
-                       0, stream, weight, wf, wb, g);
+}
+
+void launch_fwd_generic(const DcnCall &c, const float *wf, int mb, int gx)
+{
+    const dim3 grid(gx, c.g.B, (c.g.Cop / 32 + mb - 1) / mb);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.stream, c.input, c.offset, c.mask, wf, c.bias, c.output, c.g);
+    };
     switch (mb) {
-        case 8: hipLaunchKernelGGL(dcn_fwd_f32<8>, grid, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-        case 4: hipLaunchKernelGGL(dcn_fwd_f32<4>, grid, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-        case 2: hipLaunchKernelGGL(dcn_fwd_f32<2>, grid, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
-        default: hipLaunchKernelGGL(dcn_fwd_f32<1>, grid, block, 0, stream, input, offset, mask, wf, bias, output, g); break;
+        case 8: go(dcn_fwd_f32<8>); break;
+        case 4: go(dcn_fwd_f32<4>); break;
+        case 2: go(dcn_fwd_f32<2>); break;
+        default: go(dcn_fwd_f32<1>); break;
     }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
 }
 
-int dcd_dcn_v2_backward(void *stream_, const float *input, const float *weight, const float *bias,
-                        const float *offset, const float *mask, const float *grad_output, float *grad_input,
-                        float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias, int B,
-                        int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                        int dw, int dg, int precision, void *workspace, size_t workspace_bytes)
+// (1) of the generic backward: search radius from max |offset|, and the list of 32-pixel tiles with a far sample
+void launch_offset_absmax(const DcnCall &c)
 {
-    (void)bias;
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    Geom g;
-    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask ||
-        !grad_weight || !grad_bias || !workspace)
-        return DCD_ERR_BAD_ARG;
-    if (!make_geom(g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return DCD_ERR_BAD_ARG;
-    if (precision != DCD_PREC_F32 && precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
-    const bool split = precision != DCD_PREC_F32;              // the generic kernels: DCD_PREC_BF16 runs their split form
-    const bool one = precision == DCD_PREC_BF16;
-    const size_t nw = (size_t)g.Kp * g.Cop;
-    if (workspace_bytes + 256 < dcd_dcn_v2_workspace_bytes(B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg))
-        return DCD_ERR_WORKSPACE;
-    float *wf = (float *)workspace, *wb = wf + nw;
-    const size_t cells = (size_t)B * dg * g.KK * H * W;
-    InvLists inv;
-    unsigned *absmax = (unsigned *)(wb + nw);
-    inv.absmax_bits = absmax;
-    inv.cnt = (unsigned char *)absmax + 256;
-    inv.idx = (int *)(inv.cnt + (cells + 255) / 256 * 256);
-    inv.w = (float *)(inv.idx + cells * INV_CAP);
-    inv.packed = 0;
-    const size_t ntile = (size_t)B * ((g.HoWo + 31) / 32);
-    unsigned char *far_flag = (unsigned char *)(((uintptr_t)(inv.w + cells * INV_CAP) + 255) / 256 * 256);
-    int *far_list = (int *)(far_flag + (ntile + 255) / 256 * 256);
-    float *dw_part = (float *)(far_list + (ntile + 63) / 64 * 64);
-    unsigned char *blockmax = (unsigned char *)workspace + (base_workspace_bytes(g) - blockmax_bytes(g));
-    inv.blockmax = blockmax;
-    unsigned char *tileflag = (unsigned char *)workspace + (base_workspace_bytes(g) - tileflag_bytes(g));
-    inv.tileflag = nullptr;                                    // set below when the tiled grad_input kernel is in play
-    inv.flag_tx = (W + 31) / 32;
-    inv.flag_ty = (H + 3) / 4;
-    const dim3 bm_grid(((g.Ho + 7) / 8) * ((g.Wo + 7) / 8), dg * g.KK, B);
+    const Geom &g = c.g;
+    const int64_t noff = (int64_t)g.B * g.dg * 2 * g.KK * g.HoWo;
+    hipLaunchKernelGGL(dcn_offset_absmax, dim3(scan_blocks(noff)), dim3(256), 0, c.stream, c.offset, noff, c.absmax, g.HoWo,
+                       g.dg * 2 * g.KK, (g.HoWo + 31) / 32, c.far_flag, c.far_list);
+}
 
-    // one-pass backward wherever it applies (3x3 / stride 1 / pad 1, Cout <= 256; round 3: Cout <= 64 only), the dense path's
-    // layers included: 256->64 @ 24x80 0.36 vs 0.50 ms.  DCD_BWD_SWEEP=2 keeps the dense path for the layers it takes,
-    // DCD_SWEEP_WIDE=0 keeps round 3's limit of 64 outputs (A/B)
-    const char *sw_e = dcd_env("DCD_SWEEP_WIDE");              // read per call: the tests switch it inside one process
-    const bool sweep_wide = !(sw_e && atoi(sw_e) == 0);
-    // Cout 256 (the two deepest DGDE layers, Cin 512 / 256 on 12x40 / 24x80 maps) stays on the dense path when it applies: the
-    // one-pass kernel gains little there (0.68 vs 0.73 ms, 0.46 vs 0.44) and those layers' offsets (fan-in 9 Cin) are large enough in
-    // the train step to hand the call to the generic kernels (1.9 vs 0.8 ms), which the dense path does not care about
-    const bool use_sweep = sweep_ok(g) && (g.Cop <= 64 || (sweep_wide && (g.Cop <= 128 || !dense_ok(g, true)))) && dense_mode() != 1 &&
-                           (sweep_mode() == 1 || !dense_ok(g, true));
-    unsigned *dense_report = nullptr;
-    const bool far_to_dense = use_sweep && dense_ok(g, true) &&
-                              handover_far_dominated(weight, far_count_limit(g, g.Co > 64), &dense_report);
-    if ((!use_sweep || far_to_dense) && dense_ok(g, true)) {
-        ZeroRanges z;
-        for (int r = 0; r < 8; ++r) { z.p[r] = nullptr; z.n[r] = 0; }
-        z.p[0] = absmax; z.n[0] = 4;
-        z.p[1] = (unsigned *)far_flag; z.n[1] = (unsigned)((ntile + 3) / 4);
-        z.p[3] = (unsigned *)grad_bias; z.n[3] = (unsigned)Cout;
-        hipLaunchKernelGGL(dcn_zero_ranges, dim3(8), dim3(256), 0, stream, z);
-        hipLaunchKernelGGL(dcn_prep_weights, dim3((unsigned)((nw + 255) / 256 < 2048 ? (nw + 255) / 256 : 2048)), dim3(256),
-                           0, stream, weight, wf, wb, g);
-        const int64_t noff = (int64_t)B * dg * 2 * g.KK * g.HoWo;
-        int gsz = (int)((noff + 4095) / 4096);
-        if (gsz > 512) gsz = 512;
-        hipLaunchKernelGGL(dcn_offset_absmax, dim3(gsz), dim3(256), 0, stream, offset, noff, absmax, g.HoWo, dg * 2 * g.KK,
-                           (g.HoWo + 31) / 32, far_flag, far_list);
-        if (dense_report) hipLaunchKernelGGL(dcn_far_report, dim3(1), dim3(64), 0, stream, (const unsigned *)absmax, dense_report);
-        hipLaunchKernelGGL(dcn_offset_blockmax, bm_grid, dim3(64), 0, stream, offset, g, blockmax);
-        hipLaunchKernelGGL(dcn_build_inverse, dim3((H * W + 255) / 256, dg * g.KK, B), dim3(256), 0, stream, offset, mask, inv, g);
-        int splits = (int)(((int64_t)g.HoWo + 4095) / 4096);
-        if (splits > 32) splits = 32;
-        hipLaunchKernelGGL(dcn_bias_grad, dim3(Cout, splits), dim3(256), 0, stream, grad_output, grad_bias, B, Cout, g.HoWo);
-        dense_backward(stream, input, wb, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, g, inv,
-                       (float *)((char *)workspace + base_workspace_bytes(g)), precision);
-        return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+// (2) block maxima, then the inverse sample lists; only_if_far: both return at once unless the call is far-dominated
+void launch_inverse_lists(const DcnCall &c, const InvLists &inv, const unsigned *only_if_far)
+{
+    const Geom &g = c.g;
+    hipLaunchKernelGGL(dcn_offset_blockmax, dim3(((g.Ho + 7) / 8) * ((g.Wo + 7) / 8), g.dg * g.KK, g.B), dim3(64), 0, c.stream, c.offset,
+                       g, c.blockmax, only_if_far);
+    hipLaunchKernelGGL(dcn_build_inverse, dim3((g.H * g.W + 255) / 256, g.dg * g.KK, g.B), dim3(256), 0, c.stream, c.offset, c.mask, inv,
+                       g, only_if_far);
+}
+
+inline int bias_splits(const Geom &g)
+{
+    int splits = (int)(((int64_t)g.HoWo + 4095) / 4096);      // >= 4 float4 per thread and image
+    if (splits > 32) splits = 32;
+    if (splits < 1) splits = 1;
+    return splits;
+}
+
+void launch_bias_grad(const DcnCall &c)
+{
+    hipLaunchKernelGGL(dcn_bias_grad, dim3(c.g.Co, bias_splits(c.g)), dim3(256), 0, c.stream, c.grad_output, c.grad_bias, c.g.B, c.g.Co,
+                       c.g.HoWo, (const unsigned *)nullptr);
+}
+
+// (3) grad_input by gather + MFMA, register-gather form.  ab_switch: DCD_BI_MB may pin the channel blocks per workgroup;
+// partner: launched next to the tiled kernel, it only takes the tiles whose lists are too wide for that one
+void launch_bwd_input(const DcnCall &c, const InvLists &inv, bool ab_switch, int partner, const unsigned *only_if_far)
+{
+    const Geom &g = c.g;
+    const int in_tiles = (g.H * g.W + 31) / 32;
+    const int total_blocks = g.dg * (g.cpgp / 32);
+    int mbi = total_blocks >= 8 ? 8 : total_blocks >= 4 ? 4 : total_blocks >= 2 ? 2 : 1;
+    while (mbi > 1 && (int64_t)in_tiles * g.B * ((total_blocks + mbi - 1) / mbi) < 1024) mbi >>= 1;
+    if (const char *e = ab_switch ? dcd_env("DCD_BI_MB") : nullptr) {      // A/B timing of the channel blocks per workgroup
+        const int v = atoi(e);
+        if ((v == 1 || v == 2 || v == 4 || v == 8) && v <= total_blocks) mbi = v;
     }
+    const dim3 grid((in_tiles + 3) / 4, g.B, (total_blocks + mbi - 1) / mbi);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.stream, c.grad_output, c.wb, inv, c.grad_input, g, partner, only_if_far);
+    };
+    if (mbi == 8) go(dcn_bwd_input_f32<8>);
+    else if (mbi == 4) go(dcn_bwd_input_f32<4>);
+    else if (mbi == 2) go(dcn_bwd_input_f32<2>);
+    else go(dcn_bwd_input_f32<1>);
+}
+
+// tiled grad_input: one 64-channel slice per workgroup
+bool launch_bwd_input_tile(const DcnCall &c, const InvLists &inv)
+{
+    static LdsLimit lds_limit;
+    const size_t ldsb = (size_t)(BI_OC * BI_PLANE + (BI_OC / 2) * 9 * 2 * 2 * 32) * sizeof(float);
+    if (!lds_limit.raise((int)ldsb, dcn_bwd_input_tile_f32<2>)) return false;
+    const Geom &g = c.g;
+    const int tiles_x = (g.W + 31) / 32, tiles_y = (g.H + BI_TR - 1) / BI_TR;
+    hipLaunchKernelGGL(dcn_bwd_input_tile_f32<2>, dim3(tiles_x * tiles_y, g.B, (g.cpgp / 32 + 1) / 2), dim3(BI_TR * 64), ldsb, c.stream,
+                       c.grad_output, c.wb, inv, c.grad_input, g, tiles_x);
+    return true;
+}
+
+// (4) grad_offset / grad_mask (+ atomic fallback for what the lists do not cover), register-gather form over nsplit channel splits.
+// far_scal: null = every sample; the scalars = far-only next to a tiled kernel (far_list), or the whole call once it is far-dominated
+void launch_bwd_data(const DcnCall &c, const InvLists &inv, int nsplit, const unsigned *far_scal, int no_lists)
+{
+    const Geom &g = c.g;
+    const dim3 grid(((g.HoWo + 31) / 32 + 3) / 4, g.B, nsplit);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.stream, c.input, c.offset, c.mask, c.wb, c.grad_output, c.grad_input, c.grad_offset,
+                           c.grad_mask, c.grad_bias, g, nsplit, inv, far_scal, (const int *)c.far_list, no_lists);
+    };
+    if (g.Cop == 32) go(dcn_bwd_data_f32<16>);
+    else if (g.Cop == 64) go(dcn_bwd_data_f32<32>);
+    else if (g.Cop == 128) go(dcn_bwd_data_f32<64>);
+    else if (g.Cop == 256) go(dcn_bwd_data_f32<128>);
+    else go(dcn_bwd_data_f32<0>);
+}
+
+// tiled form of (4): one 32-channel block per workgroup; Cout 64, or 128 under DCD_BD_TILE128
+bool launch_bwd_data_tile(const DcnCall &c, const InvLists &inv)
+{
+    static LdsLimit lds_limit;
+    const Geom &g = c.g;
+    const size_t ldsb = (size_t)(BD_CB * BD_PLANE + 2 * g.Cop * 32) * sizeof(float);
+    if (!lds_limit.raise((int)((BD_CB * BD_PLANE + 2 * 128 * 32) * sizeof(float)), dcn_bwd_data_tile_f32<32>, dcn_bwd_data_tile_f32<64>))
+        return false;
+    const int tiles_x = (g.Wo + 31) / 32, tiles_y = (g.Ho + BD_TR - 1) / BD_TR;
+    const int nsp = g.cpgp / 32;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(tiles_x * tiles_y, g.B, nsp), dim3(BD_TR * 64), ldsb, c.stream, c.input, c.offset, c.mask, c.wb,
+                           c.grad_output, c.grad_input, c.grad_offset, c.grad_mask, g, tiles_x, nsp, inv, (const unsigned *)c.absmax);
+    };
+    if (g.Cop == 64) go(dcn_bwd_data_tile_f32<32>);
+    else go(dcn_bwd_data_tile_f32<64>);
+    return true;
+}
+
+// grad_weight, register-gather form (far_scal as in launch_bwd_data)
+void launch_bwd_weight(const DcnCall &c, const unsigned *far_scal)
+{
+    const Geom &g = c.g;
+    const int tiles = (g.HoWo + 31) / 32;
+    const int RB = g.dg * g.KK * (g.cpgp / 32);
+    const int nb = g.Cop / 32;
+    const int mb = nb >= 8 ? 8 : nb >= 4 ? 4 : nb >= 2 ? 2 : 1;
+    const int gx = (RB + 3) / 4, gz = (nb + mb - 1) / mb;
+    const int total = g.B * tiles;
+    int S = 512 / (gx * gz);
+    if (S < 1) S = 1;
+    if (S > total) S = total;
+    const size_t lds = (size_t)(4 * 32 * 33 + mb * 32 * 33) * sizeof(float);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(gx, S, gz), dim3(256), lds, c.stream, c.input, c.offset, c.mask, c.grad_output, c.grad_weight, g,
+                           tiles, S, far_scal, (const int *)c.far_list);
+    };
+    if (mb == 8) go(dcn_bwd_weight_f32<8>);
+    else if (mb == 4) go(dcn_bwd_weight_f32<4>);
+    else if (mb == 2) go(dcn_bwd_weight_f32<2>);
+    else go(dcn_bwd_weight_f32<1>);
+}
+
+// tiled grad_weight: per-workgroup partials, then their sum in a fixed order
+bool launch_bwd_weight_tile(const DcnCall &c)
+{
+    static LdsLimit lds_limit, lds_limit2, lds_limit2b;
+    const size_t ldsb = (size_t)(DW_IN_FLOATS + DW_DY_FLOATS) * sizeof(float);
+    if (!lds_limit.raise((int)ldsb, dcn_bwd_weight_tile_f32) ||
+        !lds_limit2.raise((int)(Dw2Cfg<DCD_PREC_F32>::FLOATS * sizeof(float)), dcn_bwd_weight_tile_v2<DCD_PREC_F32>) ||
+        !lds_limit2b.raise((int)(Dw2Cfg<DCD_PREC_BF16X3>::FLOATS * sizeof(float)), dcn_bwd_weight_tile_v2<DCD_PREC_BF16X3>))
+        return false;
+    static int dw_gen = 0;                                 // A/B: DCD_DW_GEN=1 keeps the first-generation f32 kernel
+    if (dw_gen == 0) {
+        const char *e = dcd_env("DCD_DW_GEN");
+        dw_gen = (e && atoi(e) == 1) ? 1 : 2;
+    }
+    static int dw_colmajor = -1;                           // A/B: DCD_DW_ORDER=0 walks the tiles row by row
+    if (dw_colmajor < 0) {
+        const char *e = dcd_env("DCD_DW_ORDER");
+        dw_colmajor = (e && atoi(e) == 0) ? 0 : 1;
+    }
+    const Geom &g = c.g;
+    float *dw_part = c.m.dw_part.in<float>(c.ws);
+    const unsigned *fs = c.absmax;
+    const int tiles_x = (g.Wo + 31) / 32, tiles_y = (g.Ho + DW_TR - 1) / DW_TR;
+    const int ncb = (g.C + DW_CB - 1) / DW_CB, nzo = (g.Co + TL_OB - 1) / TL_OB;
+    const int total = g.B * tiles_x * tiles_y;
+    int S = 512 / (ncb * nzo);
+    if (S < 1) S = 1;
+    if (S > total) S = total;
+    if (c.split)
+        hipLaunchKernelGGL(dcn_bwd_weight_tile_v2<DCD_PREC_BF16X3>, dim3(ncb, S, nzo), dim3(DW_NT),
+                           Dw2Cfg<DCD_PREC_BF16X3>::FLOATS * sizeof(float), c.stream, c.input, c.offset, c.mask, c.grad_output, dw_part, g,
+                           tiles_x, tiles_y, S, fs, dw_colmajor);
+    else if (dw_gen == 2)
+        hipLaunchKernelGGL(dcn_bwd_weight_tile_v2<DCD_PREC_F32>, dim3(ncb, S, nzo), dim3(DW_NT), Dw2Cfg<DCD_PREC_F32>::FLOATS * sizeof(float),
+                           c.stream, c.input, c.offset, c.mask, c.grad_output, dw_part, g, tiles_x, tiles_y, S, fs, dw_colmajor);
+    else
+        hipLaunchKernelGGL(dcn_bwd_weight_tile_f32, dim3(ncb, S, nzo), dim3(DW_NT), ldsb, c.stream, c.input, c.offset, c.mask,
+                           c.grad_output, dw_part, g, tiles_x, tiles_y, S, fs);
+    const int nred = ncb * nzo * 2 * 32 * DW_CB * 9;
+    const int rgroups = S >= 16 ? 16 : S;
+    hipLaunchKernelGGL(dcn_dw_reduce, dim3((nred + 255) / 256, rgroups), dim3(256), 0, c.stream, dw_part, c.grad_weight, g, ncb, nzo, S, fs);
+    return true;
+}
+
+bool launch_sweep(const DcnCall &c, const SweepArgs &a)
+{
+    static LdsLimit sw_lds_limit;
+    const int ldsb = SW_WAVES * SW_LDS_FLOATS * (int)sizeof(float);
+    if (!sw_lds_limit.raise(ldsb, dcn_bwd_sweep<DCD_PREC_F32, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16X3, 1, true>,
+                            dcn_bwd_sweep<DCD_PREC_F32, 2, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 2, false>,
+                            dcn_bwd_sweep<DCD_PREC_F32, 4, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 4, false>,
+                            dcn_bwd_sweep<DCD_PREC_BF16, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16, 2, false>,
+                            dcn_bwd_sweep<DCD_PREC_BF16, 4, false>))
+        return false;
+    auto go = [&](auto f32, auto bf16x3, auto bf16) {
+        const dim3 grid(c.m.sweep.nslot / SW_WAVES), block(64 * SW_WAVES);
+        if (c.one) hipLaunchKernelGGL(bf16, grid, block, ldsb, c.stream, a);
+        else if (c.split) hipLaunchKernelGGL(bf16x3, grid, block, ldsb, c.stream, a);
+        else hipLaunchKernelGGL(f32, grid, block, ldsb, c.stream, a);
+    };
+    if (c.m.sweep.nob == 1) go(dcn_bwd_sweep<DCD_PREC_F32, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16X3, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16, 1, true>);
+    else if (c.m.sweep.nob == 2)
+        go(dcn_bwd_sweep<DCD_PREC_F32, 2, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 2, false>, dcn_bwd_sweep<DCD_PREC_BF16, 2, false>);
+    else go(dcn_bwd_sweep<DCD_PREC_F32, 4, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 4, false>, dcn_bwd_sweep<DCD_PREC_BF16, 4, false>);
+    return true;
+}
+
+// ---- forward routes -------------------------------------------------------------------------------------------------------------
+// wide input, small map: column buffer + GEMM
+int forward_column_buffer(const DcnCall &c)
+{
+    dense_forward(c.stream, c.input, c.weight, c.bias, c.offset, c.mask, c.output, c.g, c.m, c.ws, c.precision);
+    return launch_status();
+}
+
+// workgroup-tiled LDS kernel on [Wl | Wf9 | flags], then the rescue pass: the register-gather kernel over the flagged regions only
+// (usually none: its waves exit at once)
+int forward_tiled(const DcnCall &c)
+{
+    static int rescue_taps = 0;
+    if (rescue_taps == 0) {
+        const char *e = dcd_env("DCD_FWD_RESCUE_TAPS");       // A/B: far taps in the worst wave that hand a region to the rescue kernel
+        rescue_taps = (e && atoi(e) >= 1 && atoi(e) <= 10) ? atoi(e) : 5;
+    }
+    const Geom &g = c.g;
+    const FwdTilePlan &t = c.m.tile;
+    float *wl = c.m.fwd_wl.in<float>(c.ws), *wf9 = c.m.fwd_wf9.in<float>(c.ws);
+    // region flags ("far samples dominate here: left to the rescue pass") live behind the weight area
+    unsigned char *flags = c.m.fwd_flags.in<unsigned char>(c.ws);
+    unsigned *far_count = c.m.fwd_far_count.in<unsigned>(c.ws);
+    const int64_t ncoord = (int64_t)g.B * 18 * g.HoWo;
+    const bool keeps = forward_keeps_far_samples(c.weight, ncoord);     // no far count, no rescue launch (policy above)
+    const unsigned far_limit = keeps ? 0xffffffffu : (unsigned)(ncoord / 32 < 0xffffffffll ? ncoord / 32 : 0xffffffffll);
+    const int rescue_taps_call = keeps ? 10 : rescue_taps;            // 10: no region is ever handed over (nine taps)
+    launch_prep_weights_tile(c, wl, (unsigned *)flags, wf9);
+    if (!keeps) hipLaunchKernelGGL(dcn_fwd_far_count, dim3(scan_blocks(ncoord)), dim3(256), 0, c.stream, c.offset, ncoord, far_count);
+    if (!launch_fwd_tile(c, wl, flags, wf9, rescue_taps_call, far_count, far_limit)) return DCD_ERR_LAUNCH;
+    if (keeps) return launch_status();
+    const int nb9 = g.Cop / 32, mb9 = nb9 >= 4 ? 4 : nb9 >= 2 ? 2 : 1;
+    launch_fwd9(c, wf9, mb9, (t.tiles_x * g.Ho + 3) / 4, flags, t.tiles_x, t.rows, t.nchunk);
+    return launch_status();
+}
+
+// 3x3 fast path (the only shape DGDE uses); its weights reuse the Wf area
+int forward_3x3(const DcnCall &c, int mb)
+{
+    const Geom &g = c.g;
+    float *w9 = c.m.fwd_w9.in<float>(c.ws);
+    hipLaunchKernelGGL(dcn_prep_weights9, dim3(stride_blocks((size_t)g.C * 9 * g.Cop, 2048)), dim3(256), 0, c.stream, c.weight, w9, g);
+    launch_fwd9(c, w9, mb > 4 ? 4 : mb, ((g.HoWo + 31) / 32 + 3) / 4);       // 72 VGPRs of tap state: keep <= 64 accumulator registers
+    return launch_status();
+}
+
+int forward_generic(const DcnCall &c, int mb)
+{
+    float *wf = c.m.wf.in<float>(c.ws);
+    launch_prep_weights(c, wf, c.m.wb.in<float>(c.ws));
+    launch_fwd_generic(c, wf, mb, ((c.g.HoWo + 31) / 32 + 3) / 4);
+    return launch_status();
+}
+
+// ---- backward routes ------------------------------------------------------------------------------------------------------------
+// column buffer + three products (dcn_dense.inc) behind the offset scan and the inverse lists.  report: where the call stores
+// its far count for the launch policy (null: nowhere)
+int backward_column_buffer(const DcnCall &c, unsigned *report)
+{
+    const Geom &g = c.g;
+    ZeroRanges z = {};
+    zero_range(z, 0, c.absmax, 4);
+    zero_range(z, 1, c.far_flag, ((size_t)g.B * ((g.HoWo + 31) / 32) + 3) / 4);
+    zero_range(z, 3, c.grad_bias, g.Co);
+    hipLaunchKernelGGL(dcn_zero_ranges, dim3(8), dim3(256), 0, c.stream, z);
+    launch_prep_weights(c, c.wf, c.wb);
+    launch_offset_absmax(c);
+    if (report) hipLaunchKernelGGL(dcn_far_report, dim3(1), dim3(64), 0, c.stream, (const unsigned *)c.absmax, report);
+    launch_inverse_lists(c, c.inv, nullptr);
+    launch_bias_grad(c);
+    dense_backward(c.stream, c.input, c.wb, c.offset, c.mask, c.grad_output, c.grad_input, c.grad_offset, c.grad_mask, c.grad_weight, g,
+                   c.inv, c.m, c.ws, c.precision);
+    return launch_status();
+}
+
+// One-pass backward (dcn_bwd_sweep.inc).  Near samples AND the (few) far ones: dcn_bwd_sweep.  Far samples dominating the call
+// (device-side decision from the offset scan's count): the sweep returns at once, the inverse lists are built after all and the
+// generic kernels do everything, as in the three-pass path (their launches in the hand-over tail find nothing to do otherwise).
+// Launches: prologue A (weight layouts, scalars), prologue B (zero fill, offset scan), sweep, [product], epilogue (three
+// reductions), five guarded generic kernels = 9 (round 3: 13).
+int backward_one_pass(const DcnCall &c)
+{
+    const Geom &g = c.g;
+    const SweepPlan &sp = c.m.sweep;
+    const size_t nw = (size_t)g.Kp * g.Cop;
+    const int tiles = (g.HoWo + 31) / 32;
+    float *swp = c.m.sw_wp.in<float>(c.ws), *cpart = c.m.sw_cpart.in<float>(c.ws), *dwpart = c.m.sw_dwpart.in<float>(c.ws);
+    float *col = c.m.sw_col.in<float>(c.ws);                   // nob > 1: [grad_weight product partials | col]
+    const unsigned *fs = (const unsigned *)c.absmax;
+    unsigned *far_report = nullptr;
+    const unsigned real_limit = far_count_limit(g, sp.nob > 1);
+    const int handover = handover_decide(c.stream, c.weight, real_limit, &far_report);
+    const unsigned far_limit = handover ? real_limit : FAR_COUNT_PIVOT - 1;      // "never": no kernel sees the call as far-dominated
+    {
+        // the generic kernels' weight layouts are only read after a hand-over
+        const int nb_gen = handover ? (int)stride_blocks(nw, 1024) : 0;
+        const int nb_sw = (int)stride_blocks(sp.wp_floats, 2048);
+        hipLaunchKernelGGL(dcn_sweep_prologue_a, dim3(nb_gen + nb_sw), dim3(256), 0, c.stream, c.weight, c.wf, c.wb, swp, c.absmax, g, sp.nck,
+                           sp.nob, c.split ? 1 : 0, nb_gen, far_limit);
+    }
+    {
+        ZeroRanges z = {};
+        zero_range(z, 2, c.grad_weight, (size_t)g.Co * g.C * g.KK);
+        zero_range(z, 3, c.grad_bias, g.Co);
+        zero_range(z, 4, c.grad_input, (size_t)g.B * g.C * g.H * g.W);
+        const int nb_zero = (int)(z.n[4] / 1024 + 1 < 4096 ? z.n[4] / 1024 + 1 : 4096);
+        const int64_t noff = (int64_t)g.B * 18 * g.HoWo;
+        // no tile list (far_flag = null inside): the sweep takes its far samples itself; the far-only launches of the tail then find
+        // nothing listed and return at once unless the call is handed to the generic kernels altogether
+        hipLaunchKernelGGL(dcn_sweep_prologue_b, dim3(nb_zero + scan_blocks(noff)), dim3(256), 0, c.stream, z, nb_zero, c.offset, noff,
+                           c.absmax, g.HoWo, (g.HoWo + 31) / 32);
+    }
+    {
+        SweepArgs a;
+        a.in = c.input; a.off = c.offset; a.msk = c.mask; a.wp = swp; a.gy = c.grad_output; a.gin = c.grad_input; a.cpart = cpart;
+        a.dwpart = dwpart; a.far_scal = fs; a.g = g; a.nstrip = sp.nstrip; a.nseg = sp.nseg; a.seg_rows = sp.seg_rows;
+        a.nck = sp.nck; a.nv = sp.nv; a.nslot = sp.nslot;
+        a.col = col;
+        if (!launch_sweep(c, a)) return DCD_ERR_LAUNCH;
+    }
+    {
+        SweepEpilogueArgs e;
+        e.cpart = cpart; e.gy = c.grad_output; e.dwpart = dwpart; e.goff = c.grad_offset; e.gmsk = c.grad_mask; e.gw = c.grad_weight;
+        e.gbias = c.grad_bias; e.far_scal = fs; e.g = g; e.nck = sp.nck; e.total_tiles = g.B * tiles;
+        e.far_report = far_report; e.far_base = FAR_COUNT_PIVOT - far_limit;
+        // nob == 1: the sweep's chunk-0 waves sum dY themselves (dcn_bias_grad's blocks then only act when the generic kernels
+        // take the call over)
+        e.bias_only_if_far = sp.nob == 1 ? fs : (const unsigned *)nullptr;
+        const int64_t n4 = (int64_t)g.B * 27 * g.HoWo / 4;
+        e.nb_coord = (int)stride_blocks((size_t)n4, 4096);
+        e.bias_splits = bias_splits(g);
+        int nb_dw;
+        if (sp.nob == 1) {
+            // grad_weight and grad_bias (the sweep's chunk-0 waves summed dY over their pixels) from the per-wave partials
+            const int nred = sp.nck * SW_DW_FLOATS + 64;
+            e.nvp = sp.nslot / sp.nck;
+            e.dw_bx = (nred + 255) / 256;
+            e.dw_by = e.nvp >= 64 ? 16 : (e.nvp >= 8 ? 4 : 1);
+            e.gemm_n = 0; e.gemm_S = 0;
+            nb_dw = e.dw_bx * e.dw_by;
+        } else {
+            // grad_weight = sum_b dY[b] (Cout x HoWo) col[b]^T (HoWo x 9 Cin): ONE batched product, both operands pixel-contiguous,
+            // partials per (image, pixel chunk) summed in a fixed order -- the near samples' part (the sweep's far loop wrote the
+            // far samples' masked values into col as well).  Its row index c * 9 + t IS grad_weight's layout.
+            static_assert(SW_GEMM_T == SG_T && SW_GEMM_K == SG_K, "sweep_plan sizes the product's partials with these");
+            const int K9 = g.C * 9, n = g.Co * K9;
+            SgemmArgs ga;
+            ga.A = c.grad_output; ga.B = col; ga.C = dwpart; ga.bias = nullptr; ga.M = g.Co; ga.N = K9; ga.K = g.HoWo;
+            ga.lda = g.HoWo; ga.ldb = g.HoWo; ga.ldc = K9;
+            ga.strideA = (long long)g.Co * g.HoWo; ga.strideB = (long long)K9 * g.HoWo;
+            ga.strideC = (long long)sp.dw_split * n; ga.strideCs = n;
+            ga.nsplit = sp.dw_split; ga.kchunk = sp.dw_kchunk; ga.ct = 0; ga.b_off = nullptr;
+            // far samples dominate (far_dominated, count form): the sweep wrote no columns, the generic kernels produce grad_weight
+            ga.skip_count = fs + 3; ga.skip_above = FAR_COUNT_PIVOT;
+            dense_gemm(c.stream, c.precision, true, true, ga, g.B);
+            e.nvp = 0; e.dw_bx = 0; e.dw_by = 0;
+            e.gemm_n = n; e.gemm_S = g.B * sp.dw_split;
+            nb_dw = (int)stride_blocks((size_t)(n / 4), 512);
+        }
+        hipLaunchKernelGGL(dcn_sweep_epilogue, dim3(e.nb_coord + g.Co * e.bias_splits + nb_dw), dim3(256), 0, c.stream, e);
+    }
+    if (!handover) return launch_status();
+    // hand-over tail: lists + the generic kernels, which only act when the far samples dominate (each checks the same device scalar).
+    // The data kernel's channel blocks go over grid.z (when it runs it does the whole call); with more than one block it accumulates
+    // grad_offset / grad_mask with atomics onto what the epilogue wrote (zeros then)
+    int nsplit = 1;
+    while (nsplit * 2 <= g.cpgp / 32) nsplit *= 2;
+    launch_inverse_lists(c, c.inv, fs);
+    launch_bwd_input(c, c.inv, false, 0, fs);
+    launch_bwd_data(c, c.inv, nsplit, fs, 1);
+    launch_bwd_weight(c, fs);
+    return launch_status();
+}
+
+// Generic backward: (1) offset scan, (2) inverse lists, (3) grad_input, grad_bias, (4) grad_offset / grad_mask, grad_weight; the
+// workgroup-tiled kernels first where the shape allows, each followed by its register-gather kernel for what the tiled one leaves
+int backward_three_pass(const DcnCall &c)
+{
+    const Geom &g = c.g;
     const int tiles = (g.HoWo + 31) / 32;
     const int nblk = g.cpgp / 32;
-    if (!use_sweep)
-        hipLaunchKernelGGL(dcn_prep_weights, dim3((unsigned)((nw + 255) / 256 < 2048 ? (nw + 255) / 256 : 2048)), dim3(256),
-                           0, stream, weight, wf, wb, g);
-    if (use_sweep) {
-        // ---- one-pass backward (dcn_bwd_sweep.inc).  Near samples AND the (few) far ones: dcn_bwd_sweep.  Far samples dominating the
-        // call (device-side decision from the offset scan's count): the sweep returns at once, the inverse lists are built after all
-        // and the generic kernels do everything, as in the three-pass path (their launches below find nothing to do otherwise).
-        // Launches: prologue A (weight layouts, scalars), prologue B (zero fill, offset scan), sweep, [product], epilogue (three
-        // reductions), five guarded generic kernels = 9 (round 3: 13).
-        const SweepPlan sp = sweep_plan(g);
-        float *swp = (float *)((char *)workspace + base_workspace_bytes(g) + dense_workspace_bytes(g));
-        float *cpart = swp + sp.wp_floats, *dwpart = cpart + sp.cpart_floats;
-        const unsigned *fs = (const unsigned *)absmax;
-        // the generic data kernel's channel blocks over grid.z (when it runs it does the whole call); with more than
-        // one block it accumulates grad_offset / grad_mask with atomics onto what the epilogue wrote (zeros then)
-        int nsplit = 1;
-        while (nsplit * 2 <= nblk) nsplit *= 2;
-        unsigned *far_report = nullptr;
-        const unsigned real_limit = far_count_limit(g, sp.nob > 1);
-        const int handover = handover_decide(stream, weight, real_limit, &far_report);
-        const unsigned far_limit = handover ? real_limit : FAR_COUNT_PIVOT - 1;      // "never": no kernel sees the call as far-dominated
-        {
-            // the generic kernels' weight layouts are only read after a hand-over
-            const int nb_gen = handover ? (int)((nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024) : 0;
-            const int nb_sw = (int)((sp.wp_floats + 255) / 256 < 2048 ? (sp.wp_floats + 255) / 256 : 2048);
-            hipLaunchKernelGGL(dcn_sweep_prologue_a, dim3(nb_gen + nb_sw), dim3(256), 0, stream, weight, wf, wb, swp, absmax, g, sp.nck, sp.nob,
-                               split ? 1 : 0, nb_gen, far_limit);
-        }
-        {
-            ZeroRanges z;
-            for (int r = 0; r < 8; ++r) { z.p[r] = nullptr; z.n[r] = 0; }
-            z.p[2] = (unsigned *)grad_weight; z.n[2] = (unsigned)((size_t)Cout * Cin * g.KK);
-            z.p[3] = (unsigned *)grad_bias; z.n[3] = (unsigned)Cout;
-            z.p[4] = (unsigned *)grad_input; z.n[4] = (unsigned)((size_t)B * Cin * H * W);
-            const int nb_zero = (int)(z.n[4] / 1024 + 1 < 4096 ? z.n[4] / 1024 + 1 : 4096);
-            const int64_t noff = (int64_t)B * 18 * g.HoWo;
-            int nb_scan = (int)((noff + 4095) / 4096);
-            if (nb_scan > 512) nb_scan = 512;
-            // no tile list (far_flag = null inside): the sweep takes its far samples itself; the far-only launches below then find
-            // nothing listed and return at once unless the call is handed to the generic kernels altogether
-            hipLaunchKernelGGL(dcn_sweep_prologue_b, dim3(nb_zero + nb_scan), dim3(256), 0, stream, z, nb_zero, offset, noff, absmax, g.HoWo,
-                               (g.HoWo + 31) / 32);
-        }
-        {
-            SweepArgs a;
-            a.in = input; a.off = offset; a.msk = mask; a.wp = swp; a.gy = grad_output; a.gin = grad_input; a.cpart = cpart;
-            a.dwpart = dwpart; a.far_scal = fs; a.g = g; a.nstrip = sp.nstrip; a.nseg = sp.nseg; a.seg_rows = sp.seg_rows;
-            a.nck = sp.nck; a.nv = sp.nv; a.nslot = sp.nslot;
-            a.col = dwpart + sp.dw_floats;                   // nob > 1: [grad_weight product partials | col]
-            static LdsLimit sw_lds_limit;
-            const int ldsb = SW_WAVES * SW_LDS_FLOATS * (int)sizeof(float);
-            if (!sw_lds_limit.raise(ldsb, dcn_bwd_sweep<DCD_PREC_F32, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16X3, 1, true>,
-                                    dcn_bwd_sweep<DCD_PREC_F32, 2, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 2, false>,
-                                    dcn_bwd_sweep<DCD_PREC_F32, 4, false>, dcn_bwd_sweep<DCD_PREC_BF16X3, 4, false>,
-                                    dcn_bwd_sweep<DCD_PREC_BF16, 1, true>, dcn_bwd_sweep<DCD_PREC_BF16, 2, false>,
-                                    dcn_bwd_sweep<DCD_PREC_BF16, 4, false>))
-                return DCD_ERR_LAUNCH;
-            const dim3 sgrid(sp.nslot / SW_WAVES), sblock(64 * SW_WAVES);
-#define DCD_LAUNCH_SWEEP(NOBV, DWKV)                                                                                     \
-    do {                                                                                                                \
-        if (one) hipLaunchKernelGGL((dcn_bwd_sweep<DCD_PREC_BF16, NOBV, DWKV>), sgrid, sblock, ldsb, stream, a);        \
-        else if (split) hipLaunchKernelGGL((dcn_bwd_sweep<DCD_PREC_BF16X3, NOBV, DWKV>), sgrid, sblock, ldsb, stream, a); \
-        else hipLaunchKernelGGL((dcn_bwd_sweep<DCD_PREC_F32, NOBV, DWKV>), sgrid, sblock, ldsb, stream, a);             \
-    } while (0)
-            if (sp.nob == 1) DCD_LAUNCH_SWEEP(1, true);
-            else if (sp.nob == 2) DCD_LAUNCH_SWEEP(2, false);
-            else DCD_LAUNCH_SWEEP(4, false);
-#undef DCD_LAUNCH_SWEEP
-        }
-        {
-            SweepEpilogueArgs e;
-            e.cpart = cpart; e.gy = grad_output; e.dwpart = dwpart; e.goff = grad_offset; e.gmsk = grad_mask; e.gw = grad_weight;
-            e.gbias = grad_bias; e.far_scal = fs; e.g = g; e.nck = sp.nck; e.total_tiles = B * tiles;
-            e.far_report = far_report; e.far_base = FAR_COUNT_PIVOT - far_limit;
-            // nob == 1: the sweep's chunk-0 waves sum dY themselves (dcn_bias_grad's blocks then only act when the generic kernels
-            // take the call over)
-            e.bias_only_if_far = sp.nob == 1 ? fs : (const unsigned *)nullptr;
-            const int64_t n4 = (int64_t)B * 27 * g.HoWo / 4;
-            e.nb_coord = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-            int splits = (int)(((int64_t)g.HoWo + 4095) / 4096);
-            if (splits > 32) splits = 32;
-            if (splits < 1) splits = 1;
-            e.bias_splits = splits;
-            int nb_dw;
-            if (sp.nob == 1) {
-                // grad_weight and grad_bias (the sweep's chunk-0 waves summed dY over their pixels) from the per-wave partials
-                const int nred = sp.nck * SW_DW_FLOATS + 64;
-                e.nvp = sp.nslot / sp.nck;
-                e.dw_bx = (nred + 255) / 256;
-                e.dw_by = e.nvp >= 64 ? 16 : (e.nvp >= 8 ? 4 : 1);
-                e.gemm_n = 0; e.gemm_S = 0;
-                nb_dw = e.dw_bx * e.dw_by;
-            } else {
-                // grad_weight = sum_b dY[b] (Cout x HoWo) col[b]^T (HoWo x 9 Cin): ONE batched product, both operands pixel-contiguous,
-                // partials per (image, pixel chunk) summed in a fixed order -- the near samples' part (the sweep's far loop wrote the
-                // far samples' masked values into col as well).  Its row index c * 9 + t IS grad_weight's layout.
-                static_assert(SW_GEMM_T == SG_T && SW_GEMM_K == SG_K, "sweep_plan sizes the product's partials with these");
-                const int K9 = Cin * 9, n = Cout * K9;
-                SgemmArgs ga;
-                ga.A = grad_output; ga.B = dwpart + sp.dw_floats; ga.C = dwpart; ga.bias = nullptr; ga.M = Cout; ga.N = K9; ga.K = g.HoWo;
-                ga.lda = g.HoWo; ga.ldb = g.HoWo; ga.ldc = K9;
-                ga.strideA = (long long)Cout * g.HoWo; ga.strideB = (long long)K9 * g.HoWo;
-                ga.strideC = (long long)sp.dw_split * n; ga.strideCs = n;
-                ga.nsplit = sp.dw_split; ga.kchunk = sp.dw_kchunk; ga.ct = 0; ga.b_off = nullptr;
-                // far samples dominate (far_dominated, count form): the sweep wrote no columns, the generic kernels produce grad_weight
-                ga.skip_count = fs + 3; ga.skip_above = FAR_COUNT_PIVOT;
-                if (split) sgemm_bf16x3(stream, true, true, ga, B, one);
-                else sgemm_f32(stream, true, true, ga, B);
-                e.nvp = 0; e.dw_bx = 0; e.dw_by = 0;
-                e.gemm_n = n; e.gemm_S = B * sp.dw_split;
-                nb_dw = (n / 4 + 255) / 256 < 512 ? (n / 4 + 255) / 256 : 512;
-            }
-            hipLaunchKernelGGL(dcn_sweep_epilogue, dim3(e.nb_coord + Cout * splits + nb_dw), dim3(256), 0, stream, e);
-        }
-        if (!handover) return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-        // lists + gather grad_input: only when the far samples dominate (each kernel checks the same device scalar)
-        inv.packed = 0;
-        inv.tileflag = nullptr;
-        hipLaunchKernelGGL(dcn_offset_blockmax, bm_grid, dim3(64), 0, stream, offset, g, blockmax, fs);
-        hipLaunchKernelGGL(dcn_build_inverse, dim3((H * W + 255) / 256, 9, B), dim3(256), 0, stream, offset, mask, inv, g, fs);
-        {
-            const int in_tiles = (H * W + 31) / 32;
-            int mbi = nblk >= 8 ? 8 : nblk >= 4 ? 4 : nblk >= 2 ? 2 : 1;
-            while (mbi > 1 && (int64_t)in_tiles * B * ((nblk + mbi - 1) / mbi) < 1024) mbi >>= 1;
-            dim3 grid((in_tiles + 3) / 4, B, (nblk + mbi - 1) / mbi), block(256);
-            if (mbi == 8) hipLaunchKernelGGL(dcn_bwd_input_f32<8>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, 0, fs);
-            else if (mbi == 4) hipLaunchKernelGGL(dcn_bwd_input_f32<4>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, 0, fs);
-            else if (mbi == 2) hipLaunchKernelGGL(dcn_bwd_input_f32<2>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, 0, fs);
-            else hipLaunchKernelGGL(dcn_bwd_input_f32<1>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, 0, fs);
-        }
-        {
-            dim3 grid((tiles + 3) / 4, B, nsplit), block(256);
-#define DCD_LAUNCH_BD_FAR(NS)                                                                                            \
-    hipLaunchKernelGGL(dcn_bwd_data_f32<NS>, grid, block, 0, stream, input, offset, mask, wb, grad_output, grad_input,  \
-                       grad_offset, grad_mask, grad_bias, g, nsplit, inv, fs, (const int *)far_list, 1)
-            if (g.Cop == 32) DCD_LAUNCH_BD_FAR(16);
-            else if (g.Cop == 64) DCD_LAUNCH_BD_FAR(32);
-            else if (g.Cop == 128) DCD_LAUNCH_BD_FAR(64);
-            else if (g.Cop == 256) DCD_LAUNCH_BD_FAR(128);
-            else DCD_LAUNCH_BD_FAR(0);
-#undef DCD_LAUNCH_BD_FAR
-        }
-        {
-            const int RB = 9 * nblk;
-            const int nb = g.Cop / 32;
-            const int mb = nb >= 8 ? 8 : nb >= 4 ? 4 : nb >= 2 ? 2 : 1;
-            const int gx = (RB + 3) / 4, gz = (nb + mb - 1) / mb;
-            const int total = B * tiles;
-            int S = 512 / (gx * gz);
-            if (S < 1) S = 1;
-            if (S > total) S = total;
-            dim3 grid(gx, S, gz), block(256);
-            const size_t lds = (size_t)(4 * 32 * 33 + mb * 32 * 33) * sizeof(float);
-#define DCD_LAUNCH_BW_FAR(MBV)                                                                                           \
-    hipLaunchKernelGGL(dcn_bwd_weight_f32<MBV>, grid, block, lds, stream, input, offset, mask, grad_output, grad_weight, g, \
-                       tiles, S, fs, (const int *)far_list)
-            if (mb == 8) DCD_LAUNCH_BW_FAR(8);
-            else if (mb == 4) DCD_LAUNCH_BW_FAR(4);
-            else if (mb == 2) DCD_LAUNCH_BW_FAR(2);
-            else DCD_LAUNCH_BW_FAR(1);
-#undef DCD_LAUNCH_BW_FAR
-        }
-        return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-    }
+    const size_t ntile = (size_t)g.B * tiles;
+    InvLists inv = c.inv;
+    launch_prep_weights(c, c.wf, c.wb);
     // split the channel blocks over grid.z when there are too few pixel tiles to fill the chip
     int nsplit = 1;
-    while ((int64_t)tiles * B * nsplit < 1536 && nsplit * 2 <= nblk) nsplit *= 2;
+    while ((int64_t)tiles * g.B * nsplit < 1536 && nsplit * 2 <= nblk) nsplit *= 2;
 
-    const bool tile_shape = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && dg == 1 &&
-                            (W & 3) == 0 && H >= 8 && W >= 32 && dcd_env("DCD_NO_TILE") == nullptr;
+    const bool tile_shape = dla_shape(g) && dcd_env("DCD_NO_TILE") == nullptr;
     // Cout <= 64: always.  Cout 128 (64 dY registers per lane): possible since the tap weights travel through LDS (no spills,
     // 191 VGPRs) but LDS then allows one workgroup per CU; A/B switch DCD_BD_TILE128=1.
     static int bd128 = -1;
@@ -2814,183 +2852,153 @@ int dcd_dcn_v2_backward(void *stream_, const float *input, const float *weight, 
     }
     const bool bd_tile_ok = tile_shape && (g.Cop == 64 || (g.Cop == 128 && bd128));
     {
-        ZeroRanges z;
-        for (int r = 0; r < 8; ++r) { z.p[r] = nullptr; z.n[r] = 0; }
-        z.p[0] = absmax; z.n[0] = 4;                         // max |offset| bits, far-tile count, overflowed-list count
-        z.p[1] = (unsigned *)far_flag; z.n[1] = (unsigned)((ntile + 3) / 4);
-        z.p[2] = (unsigned *)grad_weight; z.n[2] = (unsigned)((size_t)Cout * Cin * g.KK);
-        z.p[3] = (unsigned *)grad_bias; z.n[3] = (unsigned)Cout;
+        ZeroRanges z = {};
+        zero_range(z, 0, c.absmax, 4);                       // max |offset| bits, far-tile count, overflowed-list count
+        zero_range(z, 1, c.far_flag, (ntile + 3) / 4);
+        zero_range(z, 2, c.grad_weight, (size_t)g.Co * g.C * g.KK);
+        zero_range(z, 3, c.grad_bias, g.Co);
         if (nsplit > 1 || (bd_tile_ok && nblk > 1)) {      // these accumulate with atomics when the channel blocks are split
-            z.p[4] = (unsigned *)grad_offset; z.n[4] = (unsigned)((size_t)B * dg * 2 * g.KK * g.HoWo);
-            z.p[5] = (unsigned *)grad_mask; z.n[5] = (unsigned)((size_t)B * dg * g.KK * g.HoWo);
+            zero_range(z, 4, c.grad_offset, (size_t)g.B * g.dg * 2 * g.KK * g.HoWo);
+            zero_range(z, 5, c.grad_mask, (size_t)g.B * g.dg * g.KK * g.HoWo);
         }
-        z.p[6] = (unsigned *)tileflag; z.n[6] = (unsigned)(tileflag_bytes(g) / 4);
+        zero_range(z, 6, c.tileflag, c.m.tileflag.bytes / 4);
         const size_t most = (size_t)z.n[2] > (size_t)z.n[4] ? z.n[2] : z.n[4];
-        hipLaunchKernelGGL(dcn_zero_ranges, dim3((unsigned)(most / 1024 + 1 < 2048 ? most / 1024 + 1 : 2048)), dim3(256), 0, stream, z);
+        hipLaunchKernelGGL(dcn_zero_ranges, dim3((unsigned)(most / 1024 + 1 < 2048 ? most / 1024 + 1 : 2048)), dim3(256), 0, c.stream, z);
     }
+    launch_offset_absmax(c);
+    // tiled grad_input: one 64-channel slice per workgroup; wider inputs re-stage the dY window and re-read the lists per
+    // slice and lose to the register-gather kernel (measured: 128->128 1.56 vs 1.48 ms, 256->256 2.25 vs 1.64 ms per backward)
+    static int bi_nblk = 0;                                  // A/B: DCD_BI_TILE_NBLK=4 lets the tiled kernel take 128-channel inputs
+    if (bi_nblk == 0) {
+        const char *e = dcd_env("DCD_BI_TILE_NBLK");
+        bi_nblk = e ? atoi(e) : 2;
+        if (bi_nblk < 1) bi_nblk = 2;
+    }
+    const bool bi_tiled = tile_shape && nblk <= bi_nblk && (nblk <= 2 || g.Cop <= 64) && g.H < 65536 && g.W < 65536 &&
+                          dcd_env("DCD_NO_BI_TILE") == nullptr;
+    inv.packed = bi_tiled ? 1 : 0;
+    static int bi_hybrid = -1;                               // A/B: DCD_BI_HYBRID=0 -> one kernel per call, chosen by the call-wide radius
+    if (bi_hybrid < 0) {
+        const char *e = dcd_env("DCD_BI_HYBRID");
+        bi_hybrid = (e && atoi(e) == 0) ? 0 : 1;
+    }
+    inv.tileflag = (bi_tiled && bi_hybrid) ? c.tileflag : nullptr;
+    launch_inverse_lists(c, inv, nullptr);
+    if (bi_tiled && !launch_bwd_input_tile(c, inv)) return DCD_ERR_LAUNCH;
+    launch_bwd_input(c, inv, true, bi_tiled ? 1 : 0, nullptr);
+    launch_bias_grad(c);
+    if (bd_tile_ok && !launch_bwd_data_tile(c, inv)) return DCD_ERR_LAUNCH;
+    launch_bwd_data(c, inv, nsplit, bd_tile_ok ? (const unsigned *)c.absmax : nullptr, 0);
+    if (tile_shape && !launch_bwd_weight_tile(c)) return DCD_ERR_LAUNCH;
+    launch_bwd_weight(c, tile_shape ? (const unsigned *)c.absmax : nullptr);
+    return launch_status();
+}
 
-    // (1) search radius from max |offset|, (2) inverse sample lists, (3) grad_input by gather + MFMA (plain stores)
-    {
-        const int64_t noff = (int64_t)B * dg * 2 * g.KK * g.HoWo;
-        int gsz = (int)((noff + 4095) / 4096);
-        if (gsz > 512) gsz = 512;
-        hipLaunchKernelGGL(dcn_offset_absmax, dim3(gsz), dim3(256), 0, stream, offset, noff, absmax, g.HoWo, dg * 2 * g.KK,
-                           (g.HoWo + 31) / 32, far_flag, far_list);
-        const int HWin = H * W;
-#ifndef DCN_NO_BWD_TILE
-        // tiled grad_input: one 64-channel slice per workgroup; wider inputs re-stage the dY window and re-read the lists per
-        // slice and lose to the register-gather kernel (measured: 128->128 1.56 vs 1.48 ms, 256->256 2.25 vs 1.64 ms per backward)
-        static int bi_nblk = 0;                                  // A/B: DCD_BI_TILE_NBLK=4 lets the tiled kernel take 128-channel inputs
-        if (bi_nblk == 0) {
-            const char *e = dcd_env("DCD_BI_TILE_NBLK");
-            bi_nblk = e ? atoi(e) : 2;
-            if (bi_nblk < 1) bi_nblk = 2;
-        }
-        const bool bi_tile_ok = tile_shape && nblk <= bi_nblk && (nblk <= 2 || g.Cop <= 64) && H < 65536 && W < 65536 &&
-                                dcd_env("DCD_NO_BI_TILE") == nullptr;
-#else
-        const bool bi_tile_ok = false;
-#endif
-        inv.packed = bi_tile_ok ? 1 : 0;
-        static int bi_hybrid = -1;                               // A/B: DCD_BI_HYBRID=0 -> one kernel per call, chosen by the call-wide radius
-        if (bi_hybrid < 0) {
-            const char *e = dcd_env("DCD_BI_HYBRID");
-            bi_hybrid = (e && atoi(e) == 0) ? 0 : 1;
-        }
-        inv.tileflag = (bi_tile_ok && bi_hybrid) ? tileflag : nullptr;
-        hipLaunchKernelGGL(dcn_offset_blockmax, bm_grid, dim3(64), 0, stream, offset, g, blockmax);
-        hipLaunchKernelGGL(dcn_build_inverse, dim3((HWin + 255) / 256, dg * g.KK, B), dim3(256), 0, stream, offset, mask, inv, g);
-        bool bi_tiled = false;
-#ifndef DCN_NO_BWD_TILE
-        if (bi_tile_ok) {
-            static LdsLimit lds_limit;
-            const size_t ldsb = (size_t)(BI_OC * BI_PLANE + (BI_OC / 2) * 9 * 2 * 2 * 32) * sizeof(float);
-            if (!lds_limit.raise((int)ldsb, dcn_bwd_input_tile_f32<2>)) return DCD_ERR_LAUNCH;
-            const int tiles_x = (W + 31) / 32, tiles_y = (H + BI_TR - 1) / BI_TR;
-            hipLaunchKernelGGL(dcn_bwd_input_tile_f32<2>, dim3(tiles_x * tiles_y, B, (nblk + 1) / 2), dim3(BI_TR * 64), ldsb, stream,
-                               grad_output, wb, inv, grad_input, g, tiles_x);
-            bi_tiled = true;
-        }
-#endif
-        const int in_tiles = (HWin + 31) / 32;
-        const int total_blocks = dg * nblk;
-        int mbi = total_blocks >= 8 ? 8 : total_blocks >= 4 ? 4 : total_blocks >= 2 ? 2 : 1;
-        while (mbi > 1 && (int64_t)in_tiles * B * ((total_blocks + mbi - 1) / mbi) < 1024) mbi >>= 1;
-        if (const char *e = dcd_env("DCD_BI_MB")) {              // A/B timing of the channel blocks per workgroup
-            const int v = atoi(e);
-            if ((v == 1 || v == 2 || v == 4 || v == 8) && v <= total_blocks) mbi = v;
-        }
-        dim3 grid((in_tiles + 3) / 4, B, (total_blocks + mbi - 1) / mbi), block(256);
-        const int partner = bi_tiled ? 1 : 0;     // with the tiled kernel launched, this one only runs when the lists are too wide for it
-        if (mbi == 8) hipLaunchKernelGGL(dcn_bwd_input_f32<8>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, partner);
-        else if (mbi == 4) hipLaunchKernelGGL(dcn_bwd_input_f32<4>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, partner);
-        else if (mbi == 2) hipLaunchKernelGGL(dcn_bwd_input_f32<2>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, partner);
-        else hipLaunchKernelGGL(dcn_bwd_input_f32<1>, grid, block, 0, stream, grad_output, wb, inv, grad_input, g, partner);
+}  // namespace
+
+extern "C" {
+
+size_t dcd_dcn_v2_workspace_bytes(int B, int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph,
+                                  int pw, int dh, int dw, int dg)
+{
+    Geom g;
+    if (!make_geom(g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return 0;
+    return dcn_workspace_backward(g).total;
+}
+
+int dcd_dcn_v2_forward(void *stream_, const float *input, const float *weight, const float *bias,
+                       const float *offset, const float *mask, float *output, int B, int Cin, int H, int W,
+                       int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg,
+                       int precision, void *workspace, size_t workspace_bytes)
+{
+    (void)hipGetLastError();
+    DcnCall c;
+    if (!input || !weight || !bias || !offset || !mask || !output || !workspace) return DCD_ERR_BAD_ARG;
+    if (!make_geom(c.g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return DCD_ERR_BAD_ARG;
+    // DCD_PREC_BF16X3 permits (does not oblige) the split-bf16 contraction: the workgroup-tiled kernels have it, every other
+    // geometry runs the exact fp32 kernels, which are inside any tolerance the split form is
+    // DCD_PREC_BF16 (one product of bf16-rounded operands): the same kernels and prepared weights, their low halves unread
+    if (precision != DCD_PREC_F32 && precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
+    c.stream = (hipStream_t)stream_;
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = offset; c.mask = mask; c.output = output;
+    c.precision = precision;
+    c.split = precision != DCD_PREC_F32;
+    c.one = precision == DCD_PREC_BF16;
+    c.ws = workspace;
+    c.m = dcn_workspace_forward(c.g, c.split);
+    const DcnWorkspace &m = c.m;
+    if (workspace_bytes < m.wb.end()) return DCD_ERR_WORKSPACE;
+    if (dense_ok(c.g, false)) {
+        if (workspace_bytes < m.dense_end) return DCD_ERR_WORKSPACE;
+        return forward_column_buffer(c);
     }
-    {
-        int splits = (int)(((int64_t)g.HoWo + 4095) / 4096);      // >= 4 float4 per thread and image
-        if (splits > 32) splits = 32;
-        if (splits < 1) splits = 1;
-        hipLaunchKernelGGL(dcn_bias_grad, dim3(Cout, splits), dim3(256), 0, stream, grad_output, grad_bias, B, Cout, g.HoWo);
-    }
-    // (4) grad_offset / grad_mask (+ atomic fallback for what the lists do not cover)
-    bool bd_tiled = false;
-#ifndef DCN_NO_BWD_TILE
-    if (bd_tile_ok) {
-        static LdsLimit lds_limit;
-        const size_t ldsb = (size_t)(BD_CB * BD_PLANE + 2 * g.Cop * 32) * sizeof(float);
-        if (!lds_limit.raise((int)((BD_CB * BD_PLANE + 2 * 128 * 32) * sizeof(float)), dcn_bwd_data_tile_f32<32>, dcn_bwd_data_tile_f32<64>))
-            return DCD_ERR_LAUNCH;
-        const int tiles_x = (g.Wo + 31) / 32, tiles_y = (g.Ho + BD_TR - 1) / BD_TR;
-        const int nsp = nblk;                 // one 32-channel block per workgroup
-        dim3 gridt(tiles_x * tiles_y, B, nsp), blockt(BD_TR * 64);
-        if (g.Cop == 64)
-            hipLaunchKernelGGL(dcn_bwd_data_tile_f32<32>, gridt, blockt, ldsb, stream, input, offset, mask, wb, grad_output, grad_input,
-                               grad_offset, grad_mask, g, tiles_x, nsp, inv, (const unsigned *)absmax);
-        else
-            hipLaunchKernelGGL(dcn_bwd_data_tile_f32<64>, gridt, blockt, ldsb, stream, input, offset, mask, wb, grad_output, grad_input,
-                               grad_offset, grad_mask, g, tiles_x, nsp, inv, (const unsigned *)absmax);
-        bd_tiled = true;
-    }
-#endif
-    {
-        dim3 grid((tiles + 3) / 4, B, nsplit), block(256);
-        const int ns = g.Cop / 2;
-#define DCD_LAUNCH_BD(NS)                                                                                          \
-    hipLaunchKernelGGL(dcn_bwd_data_f32<NS>, grid, block, 0, stream, input, offset, mask, wb, grad_output, grad_input, \
-                       grad_offset, grad_mask, grad_bias, g, nsplit, inv, bd_tiled ? (const unsigned *)absmax : (const unsigned *)nullptr, \
-                       (const int *)far_list)
-        if (ns == 16) DCD_LAUNCH_BD(16);
-        else if (ns == 32) DCD_LAUNCH_BD(32);
-        else if (ns == 64) DCD_LAUNCH_BD(64);
-        else if (ns == 128) DCD_LAUNCH_BD(128);
-        else DCD_LAUNCH_BD(0);
-#undef DCD_LAUNCH_BD
-    }
-    bool dw_tiled = false;
-#ifndef DCN_NO_BWD_TILE
-    if (tile_shape) {
-        static LdsLimit lds_limit, lds_limit2, lds_limit2b;
-        const size_t ldsb = (size_t)(DW_IN_FLOATS + DW_DY_FLOATS) * sizeof(float);
-        if (!lds_limit.raise((int)ldsb, dcn_bwd_weight_tile_f32) ||
-            !lds_limit2.raise((int)(Dw2Cfg<DCD_PREC_F32>::FLOATS * sizeof(float)), dcn_bwd_weight_tile_v2<DCD_PREC_F32>) ||
-            !lds_limit2b.raise((int)(Dw2Cfg<DCD_PREC_BF16X3>::FLOATS * sizeof(float)), dcn_bwd_weight_tile_v2<DCD_PREC_BF16X3>))
-            return DCD_ERR_LAUNCH;
-        static int dw_gen = 0;                                 // A/B: DCD_DW_GEN=1 keeps the first-generation f32 kernel
-        if (dw_gen == 0) {
-            const char *e = dcd_env("DCD_DW_GEN");
-            dw_gen = (e && atoi(e) == 1) ? 1 : 2;
-        }
-        static int dw_colmajor = -1;                           // A/B: DCD_DW_ORDER=0 walks the tiles row by row
-        if (dw_colmajor < 0) {
-            const char *e = dcd_env("DCD_DW_ORDER");
-            dw_colmajor = (e && atoi(e) == 0) ? 0 : 1;
-        }
-        const int tiles_x = (g.Wo + 31) / 32, tiles_y = (g.Ho + DW_TR - 1) / DW_TR;
-        const int ncb = (Cin + DW_CB - 1) / DW_CB, nzo = (Cout + TL_OB - 1) / TL_OB;
-        const int total = B * tiles_x * tiles_y;
-        int S = 512 / (ncb * nzo);
-        if (S < 1) S = 1;
-        if (S > total) S = total;
-        if (split)
-            hipLaunchKernelGGL(dcn_bwd_weight_tile_v2<DCD_PREC_BF16X3>, dim3(ncb, S, nzo), dim3(DW_NT),
-                               Dw2Cfg<DCD_PREC_BF16X3>::FLOATS * sizeof(float), stream, input, offset, mask, grad_output, dw_part, g,
-                               tiles_x, tiles_y, S, (const unsigned *)absmax, dw_colmajor);
-        else if (dw_gen == 2)
-            hipLaunchKernelGGL(dcn_bwd_weight_tile_v2<DCD_PREC_F32>, dim3(ncb, S, nzo), dim3(DW_NT),
-                               Dw2Cfg<DCD_PREC_F32>::FLOATS * sizeof(float), stream, input, offset, mask, grad_output, dw_part, g,
-                               tiles_x, tiles_y, S, (const unsigned *)absmax, dw_colmajor);
-        else
-            hipLaunchKernelGGL(dcn_bwd_weight_tile_f32, dim3(ncb, S, nzo), dim3(DW_NT), ldsb, stream, input, offset, mask, grad_output,
-                               dw_part, g, tiles_x, tiles_y, S, (const unsigned *)absmax);
-        const int nred = ncb * nzo * 2 * 32 * DW_CB * 9;
-        const int rgroups = S >= 16 ? 16 : S;
-        hipLaunchKernelGGL(dcn_dw_reduce, dim3((nred + 255) / 256, rgroups), dim3(256), 0, stream, dw_part, grad_weight, g, ncb, nzo, S,
-                           (const unsigned *)absmax);
-        dw_tiled = true;
-    }
-#endif
-    {
-        const int RB = dg * g.KK * nblk;
-        const int nb = g.Cop / 32;
-        const int mb = nb >= 8 ? 8 : nb >= 4 ? 4 : nb >= 2 ? 2 : 1;
-        const int gx = (RB + 3) / 4, gz = (nb + mb - 1) / mb;
-        const int total = B * tiles;
-        int S = 512 / (gx * gz);
-        if (S < 1) S = 1;
-        if (S > total) S = total;
-        dim3 grid(gx, S, gz), block(256);
-        const size_t lds = (size_t)(4 * 32 * 33 + mb * 32 * 33) * sizeof(float);
-#define DCD_LAUNCH_BW(MBV)                                                                                        \
-    hipLaunchKernelGGL(dcn_bwd_weight_f32<MBV>, grid, block, lds, stream, input, offset, mask, grad_output, grad_weight, g, \
-                       tiles, S, dw_tiled ? (const unsigned *)absmax : (const unsigned *)nullptr, (const int *)far_list)
-        if (mb == 8) DCD_LAUNCH_BW(8);
-        else if (mb == 4) DCD_LAUNCH_BW(4);
-        else if (mb == 2) DCD_LAUNCH_BW(2);
-        else DCD_LAUNCH_BW(1);
-#undef DCD_LAUNCH_BW
-    }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    // the tile route when its overlays fit: Wl in the Wf area, Wf9 in the Wb area, flags and far counter inside the caller's buffer;
+    // otherwise the routes below, which need [Wf | Wb] at most
+    if (m.has_tile && m.fwd_wl.bytes <= m.wf.bytes && m.fwd_wf9.bytes <= m.wb.bytes && workspace_bytes >= m.fwd_far_count.end())
+        return forward_tiled(c);
+    const int mb = pick_mb(c.g.Cop / 32, (c.g.HoWo + 31) / 32 * B);
+    if (c.g.KK == 9 && W >= 2 && m.fwd_w9.bytes <= m.wf.bytes) return forward_3x3(c, mb);
+    return forward_generic(c, mb);
+}
+
+int dcd_dcn_v2_backward(void *stream_, const float *input, const float *weight, const float *bias,
+                        const float *offset, const float *mask, const float *grad_output, float *grad_input,
+                        float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias, int B,
+                        int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                        int dw, int dg, int precision, void *workspace, size_t workspace_bytes)
+{
+    (void)hipGetLastError();
+    DcnCall c;
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask ||
+        !grad_weight || !grad_bias || !workspace)
+        return DCD_ERR_BAD_ARG;
+    if (!make_geom(c.g, B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return DCD_ERR_BAD_ARG;
+    if (precision != DCD_PREC_F32 && precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
+    const Geom &g = c.g;
+    c.stream = (hipStream_t)stream_;
+    c.input = input; c.weight = weight; c.bias = bias; c.offset = offset; c.mask = mask; c.grad_output = grad_output;
+    c.grad_input = grad_input; c.grad_offset = grad_offset; c.grad_mask = grad_mask; c.grad_weight = grad_weight; c.grad_bias = grad_bias;
+    c.precision = precision;
+    c.split = precision != DCD_PREC_F32;
+    c.one = precision == DCD_PREC_BF16;
+    c.ws = workspace;
+    c.m = dcn_workspace_backward(g);
+    const DcnWorkspace &m = c.m;
+    // 256 bytes short is accepted: when the map ends with the column-buffer or the one-pass bracket, its last 256 bytes are the
+    // unused tail every bracket's size has carried since the first layout.  (A map that ends with the first bracket has no such
+    // tail: there the tile flags reach the advertised end.)
+    if (workspace_bytes + 256 < m.total) return DCD_ERR_WORKSPACE;
+    c.wf = m.wf.in<float>(workspace);
+    c.wb = m.wb.in<float>(workspace);
+    c.absmax = m.scalars.in<unsigned>(workspace);
+    c.far_flag = m.far_flag.in<unsigned char>(workspace);
+    c.far_list = m.far_list.in<int>(workspace);
+    c.blockmax = m.blockmax.in<unsigned char>(workspace);
+    c.tileflag = m.tileflag.in<unsigned char>(workspace);
+    c.inv.absmax_bits = c.absmax;
+    c.inv.cnt = m.inv_cnt.in<unsigned char>(workspace);
+    c.inv.idx = m.inv_idx.in<int>(workspace);
+    c.inv.w = m.inv_w.in<float>(workspace);
+    c.inv.packed = 0;
+    c.inv.blockmax = c.blockmax;
+    c.inv.tileflag = nullptr;
+    c.inv.flag_tx = (W + 31) / 32;
+    c.inv.flag_ty = (H + 3) / 4;
+
+    // one-pass backward wherever it applies (3x3 / stride 1 / pad 1, Cout <= 256; round 3: Cout <= 64 only), the dense path's
+    // layers included: 256->64 @ 24x80 0.36 vs 0.50 ms.  DCD_BWD_SWEEP=2 keeps the dense path for the layers it takes,
+    // DCD_SWEEP_WIDE=0 keeps round 3's limit of 64 outputs (A/B)
+    const char *sw_e = dcd_env("DCD_SWEEP_WIDE");              // read per call: the tests switch it inside one process
+    const bool sweep_wide = !(sw_e && atoi(sw_e) == 0);
+    // Cout 256 (the two deepest DGDE layers, Cin 512 / 256 on 12x40 / 24x80 maps) stays on the dense path when it applies: the
+    // one-pass kernel gains little there (0.68 vs 0.73 ms, 0.46 vs 0.44) and those layers' offsets (fan-in 9 Cin) are large enough in
+    // the train step to hand the call to the generic kernels (1.9 vs 0.8 ms), which the dense path does not care about
+    const bool use_sweep = m.has_sweep && (g.Cop <= 64 || (sweep_wide && (g.Cop <= 128 || !m.has_dense))) && dense_mode() != 1 &&
+                           (sweep_mode() == 1 || !m.has_dense);
+    unsigned *dense_report = nullptr;
+    const bool far_to_dense = use_sweep && m.has_dense && handover_far_dominated(weight, far_count_limit(g, g.Co > 64), &dense_report);
+    if ((!use_sweep || far_to_dense) && m.has_dense) return backward_column_buffer(c, dense_report);
+    return use_sweep ? backward_one_pass(c) : backward_three_pass(c);
 }
 
 #ifdef SW_PROFILE

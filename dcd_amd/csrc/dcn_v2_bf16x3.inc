@@ -74,8 +74,6 @@ __device__ __forceinline__ f32x16 mfma_bf16x3(const bf16x8 &a_hi, const bf16x8 &
 // TR = 4: one LDS buffer (66 KB), two workgroups per CU; the next chunk travels through registers during the MFMA work and
 //         is written between two barriers.
 // ---------------------------------------------------------------------------------------------
-constexpr int TB_CH = 16;
-constexpr int TB_W_FLOATS = 9 * 2 * 2 * 64 * 4;          // 9216 dwords (18 432 bf16) per (slice, chunk)
 constexpr int TB_NW = TB_W_FLOATS / 4;                   // 2304 dwordx4
 template <int TR> struct TileCfgB {
     static constexpr int WH = TR + 8;

@@ -15,14 +15,10 @@
 // issued before the 32 MFMAs of step s and written to LDS after them.  Operand reads are ds_read2_b32 (the lane's two
 // blocks are 32 floats apart): two per four MFMAs.
 #pragma once
+#include "sgemm_tile.h"
 
 namespace {
 
-constexpr int SG_T = 128;        // tile edge
-#ifndef SG_K_STEP
-#define SG_K_STEP 16
-#endif
-constexpr int SG_K = SG_K_STEP;  // k per step
 constexpr int SG_S = SG_T + 4;   // LDS row stride (floats)
 
 template <int N> struct IntK { static constexpr int value = N; };

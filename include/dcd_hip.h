@@ -91,7 +91,9 @@ const char *dcd_version(void);
  *                                ~2^-9 relative per operand.  Permits, does not oblige (kernels without the one-product
  *                                form run the split-bf16 or the exact fp32 one).
  * workspace: device scratch of at least dcd_dcn_v2_workspace_bytes(...) bytes, 256-byte aligned,
- *            owned by the caller; contents are dead after the call's kernels complete.
+ *            owned by the caller; contents are dead after the call's kernels complete.  Its layout -- byte offset and length of
+ *            every region, for both passes -- is csrc/dcn_workspace.h (DcnWorkspace); the size depends on the per-call
+ *            switches DCD_DCN_DENSE and DCD_BWD_SWEEP, so query it under the environment of the call.
  * ---------------------------------------------------------------------------------------------- */
 #define DCD_PREC_F32 0
 #define DCD_PREC_BF16X3 1
