@@ -24,6 +24,7 @@
 
 #include "../../include/dcd_hip.h"
 #include "tuning_env.h"
+#include "conv_plan.h"
 #include "lds_limit.h"
 #include "bf16_split.h"
 
@@ -33,7 +34,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr int WN_CH = 8;                          // input channels per chunk
+// (input channels per chunk -- WN_CH = 8 here, WS_CH, DC_CH -- are in conv_plan.h: the host's plans count chunks too)
 // output channels per workgroup: 32 NB (NB = 2; NB = 1 for layers of at most 32 outputs -- DCN's 27-channel offset convs)
 constexpr int WN_NT = 512;
 
@@ -381,7 +382,6 @@ __global__ __launch_bounds__(WN_NT) void wino_conv3x3_f32(const float *__restric
 //     i = 0..7, of the chunk (the weights are prepared in the same order), so the two lane halves read planes of opposite bank
 //     parity exactly like the fp32 kernel;
 //   * region geometry <2,16> only (the 12 x 20 px regions' window does not fit beside two 64 KB weight buffers).
-constexpr int WS_CH = 16;
 
 template <int NB>
 __device__ __forceinline__ void wino_prep_split_body(const float *__restrict__ w, unsigned *__restrict__ us, int Cc, int Kk, int mode,
@@ -1016,13 +1016,7 @@ __global__ __launch_bounds__(256) void wino_wrw_reduce(const float *__restrict__
 
 }  // namespace
 
-// Region geometry and contraction split of one call.  The workgroup holds 103 KB of LDS and 8 waves with 128 accumulator
-// registers each, so exactly one sits on a CU: time ~ rounds of `cus` workgroups x chunks per workgroup.
-struct ConvPlan {
-    int geom;          // 0: 8 x 32 px regions, 1: 12 x 20 px
-    int nb;            // 32-channel output blocks per workgroup: 2, or 1 for layers of at most 32 outputs
-    int tiles_x, tiles_y, nchunk, nz, ksplit;
-};
+// ---- host side: every entry point reads "validate, plan, check the workspace, launch"; the arithmetic is in conv_plan.h ----------
 
 static int device_cus()
 {
@@ -1036,233 +1030,233 @@ static int device_cus()
     return cus;
 }
 
-static ConvPlan conv_plan(int B, int Cc, int H, int W, int Kk)
+static int launch_status() { return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH; }
+
+// blocks of 256 threads for n items, at most `cap` (the kernels stride over the rest)
+static int blocks256(size_t n, size_t cap) { return (int)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
+
+// true when the listed kernels may use ldsb bytes of dynamic LDS on this device: one LdsLimit per list of kernels
+template <auto... Kernels>
+static bool lds_ok(size_t ldsb)
 {
-    ConvPlan best{};
-    const int cus = device_cus();
-    int64_t best_cost = -1;
-    for (int g = 0; g < 2; ++g) {
-        ConvPlan p;
-        p.geom = g;
-        p.tiles_x = g == 0 ? (W + 31) / 32 : (W + 19) / 20;
-        p.tiles_y = g == 0 ? (H + 7) / 8 : (H + 11) / 12;
-        p.nchunk = (Cc + WN_CH - 1) / WN_CH;
-        p.nb = Kk <= 32 ? 1 : 2;
-        p.nz = (Kk + 32 * p.nb - 1) / (32 * p.nb);
-        const int64_t wgs = (int64_t)p.tiles_x * p.tiles_y * B * p.nz;
-        // split the contraction while the launch leaves CUs idle and a split keeps at least 4 chunks (its output transform
-        // and the partial image it writes are not free; 4 vs 8: one image per GPU, 256 -> 256 @ 24x80 39 -> 32 us)
-        static const int min_chunks = dcd_env("DCD_CONV_MINCHUNK") ? atoi(dcd_env("DCD_CONV_MINCHUNK")) : 4;
-        int ks = 1;
-        while (ks < 8 && wgs * (ks * 2) <= cus && p.nchunk / (ks * 2) >= min_chunks) ks *= 2;
-        p.ksplit = ks;
-        const int64_t rounds = (wgs * ks + cus - 1) / cus;
-        const int64_t cost = rounds * ((p.nchunk + ks - 1) / ks + 2) * (g == 0 ? 16 : 17);     // 12x20: 30 of 32 lanes, more halo
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = p;
-        }
-    }
-    return best;
+    static LdsLimit lds_limit;
+    return lds_limit.raise((int)ldsb, Kernels...);
+}
+
+// One 3x3 / stride 1 call as its launchers see it: input (B, Cc, H, W) -> output (B, Kk, H, W), splits >= 1 into part.
+struct ConvCall {
+    hipStream_t stream;
+    ConvPlan pl;
+    const float *input;
+    const void *weights;               // of this direction, in the form's own layout
+    float *output, *part;
+    const float *bias, *residual;
+    int B, Cc, H, W, Kk;
+};
+
+// the three forms' kernels take the same arguments on the same grid
+template <auto Kernel, typename Weight>
+static int conv_launch(const ConvCall &c, int threads, size_t ldsb)
+{
+    if (!lds_ok<Kernel>(ldsb)) return DCD_ERR_LAUNCH;
+    hipLaunchKernelGGL(Kernel, dim3(c.pl.tiles_x * c.pl.tiles_y, c.B, c.pl.nz * c.pl.ksplit), dim3(threads), ldsb, c.stream, c.input,
+                       (const Weight *)c.weights, c.output, c.part, c.bias, c.residual, c.Cc, c.H, c.W, c.Kk, c.pl.tiles_x, c.pl.nchunk,
+                       c.pl.nz);
+    return DCD_OK;
 }
 
 template <int TR, int TC, int NB>
-static int conv_launch(hipStream_t stream, const ConvPlan &pl, const float *input, const float *ul, float *output, float *part,
-                       const float *bias, const float *residual, int B, int Cc, int H, int W, int Kk)
+static int conv_launch_f32(const ConvCall &c)
 {
-    static LdsLimit lds_limit;
     size_t ldsb = (size_t)2 * WinoGeom<TR, TC, NB>::BUF * sizeof(float);
     if (ldsb < (size_t)8 * 32 * 64 * sizeof(float)) ldsb = (size_t)8 * 32 * 64 * sizeof(float);      // the epilogue's exchange
-    if (!lds_limit.raise((int)ldsb, wino_conv3x3_f32<TR, TC, NB>)) return DCD_ERR_LAUNCH;
-    hipLaunchKernelGGL((wino_conv3x3_f32<TR, TC, NB>), dim3(pl.tiles_x * pl.tiles_y, B, pl.nz * pl.ksplit), dim3(WN_NT), ldsb, stream,
-                       input, ul, output, part, bias, residual, Cc, H, W, Kk, pl.tiles_x, pl.nchunk, pl.nz);
-    return DCD_OK;
+    return conv_launch<wino_conv3x3_f32<TR, TC, NB>, float>(c, WN_NT, ldsb);
 }
 
 template <int NB, int NP>
-static int conv_launch_split(hipStream_t stream, const ConvPlan &pl, const float *input, const unsigned *us, float *output, float *part,
-                             const float *bias, const float *residual, int B, int Cc, int H, int W, int Kk)
+static int conv_launch_split(const ConvCall &c)
 {
-    static LdsLimit lds_limit;
     using G = WinoGeom<2, 16, NB>;
     const size_t ldsb = ((size_t)((WS_CH * G::PLANE + 3) & ~3) + (size_t)2 * 16 * NB * 2 * 256) * sizeof(float);
-    if (!lds_limit.raise((int)ldsb, wino_conv3x3_split<NB, NP>)) return DCD_ERR_LAUNCH;
-    hipLaunchKernelGGL((wino_conv3x3_split<NB, NP>), dim3(pl.tiles_x * pl.tiles_y, B, pl.nz * pl.ksplit), dim3(WN_NT), ldsb, stream, input,
-                       us, output, part, bias, residual, Cc, H, W, Kk, pl.tiles_x, pl.nchunk, pl.nz);
-    return DCD_OK;
+    return conv_launch<wino_conv3x3_split<NB, NP>, unsigned>(c, WN_NT, ldsb);
 }
 
-// split-bf16 form: 8 x 32 px regions, chunks of 16 channels; the contraction is split while CUs would idle and a split keeps two chunks
-static ConvPlan conv_plan_split(int B, int Cc, int H, int W, int Kk)
-{
-    ConvPlan p;
-    p.geom = 0;
-    p.tiles_x = (W + 31) / 32;
-    p.tiles_y = (H + 7) / 8;
-    p.nchunk = (Cc + WS_CH - 1) / WS_CH;
-    p.nb = Kk <= 32 ? 1 : 2;
-    p.nz = (Kk + 32 * p.nb - 1) / (32 * p.nb);
-    const int64_t wgs = (int64_t)p.tiles_x * p.tiles_y * B * p.nz;
-    const int cus = device_cus();
-    int ks = 1;
-    while (ks < 8 && wgs * (ks * 2) <= cus && p.nchunk / (ks * 2) >= 2) ks *= 2;
-    p.ksplit = ks;
-    return p;
-}
-
-// direct one-product form (conv_direct_bf16.inc): rows per wave P (plan.geom) = 4 or 2, i.e. 16 x 32 or 8 x 32 px regions
-static bool conv_direct_ok(int Cc, int H, int W)
-{
-    return (int64_t)(Cc + DC_CH) * H * W < (1ll << 29);
-}
-
-static ConvPlan conv_plan_direct(int B, int Cc, int H, int W, int Kk)
-{
-    static const int pin = dcd_env("DCD_CONV_DIRECT_P") ? atoi(dcd_env("DCD_CONV_DIRECT_P")) : 0;
-    const int cus = device_cus();
-    ConvPlan best{};
-    int64_t best_cost = -1;
-    for (int P = 2; P <= 4; P += 2) {
-        if (P != (pin == 4 ? 4 : 2)) continue;                       // 16 x 32 px regions (one workgroup per CU) only when pinned
-        ConvPlan p;
-        // 8 x 64 px regions (eight waves) where the width divides: a third less L2 traffic for the column halo
-        static const int wxpin = dcd_env("DCD_CONV_DIRECT_WX") ? atoi(dcd_env("DCD_CONV_DIRECT_WX")) : 0;
-        const int wx = P == 2 && wxpin == 2 ? 2 : 1;
-        p.geom = P | (wx << 4);
-        p.tiles_x = (W + 32 * wx - 1) / (32 * wx);
-        p.tiles_y = (H + 4 * P - 1) / (4 * P);
-        p.nchunk = (Cc + DC_CH - 1) / DC_CH;
-        p.nb = Kk <= 32 ? 1 : 2;
-        p.nz = (Kk + 32 * p.nb - 1) / (32 * p.nb);
-        const int64_t wgs = (int64_t)p.tiles_x * p.tiles_y * B * p.nz;
-        // Three workgroups share a CU.  A long contraction is split while slots would stay empty and a split keeps 16 chunks
-        // (256 -> 256 @ 24x80 x 8: 46.5 us split in two or not, and the split pays a wino_sum_partials launch); a launch of less
-        // than 1.5 workgroups per CU (one or two images per GPU) is split down to two chunks -- there a workgroup's chunks are a
-        // serial chain of load latencies (256 -> 256 @ 24x80 x 1: 27.7 us unsplit against the Winograd form's 14.5).
-        static const int min_chunks = dcd_env("DCD_CONV_DIRECT_MINCHUNK") ? atoi(dcd_env("DCD_CONV_DIRECT_MINCHUNK")) : 16;
-        int ks = 1;
-        while (ks < 8) {
-            const int64_t next = wgs * ks * 2;
-            const int left = p.nchunk / (ks * 2);
-            const bool fill = next <= 3 * cus && left >= min_chunks;
-            const bool small = 2 * next <= 3 * cus && left >= 2;
-            if (!fill && !small) break;
-            ks *= 2;
-        }
-        p.ksplit = ks;
-        best = p;
-    }
-    (void)best_cost;
-    return best;
-}
-
+// MODE: 0 weights resident, 1 window resident, 2 both streamed
 template <int NB, int P, int MODE, int WX>
-static int conv_launch_direct(hipStream_t stream, const ConvPlan &pl, const float *input, const unsigned *wd, float *output, float *part,
-                              const float *bias, const float *residual, int B, int Cc, int H, int W, int Kk)
+static int conv_launch_direct(const ConvCall &c)
 {
-    static LdsLimit lds_limit;
     const size_t ldsb = ((size_t)2 * (4 * P + 2) * (32 * WX + 8) + (size_t)2 * 9 * NB * 64) * 16;
-    if constexpr (MODE == 2) {
-        if (!lds_limit.raise((int)ldsb, conv3x3_direct_bf16_w4<NB, P, WX>)) return DCD_ERR_LAUNCH;
-        hipLaunchKernelGGL((conv3x3_direct_bf16_w4<NB, P, WX>), dim3(pl.tiles_x * pl.tiles_y, B, pl.nz * pl.ksplit), dim3(DC_NT * WX), ldsb,
-                           stream, input, wd, output, part, bias, residual, Cc, H, W, Kk, pl.tiles_x, pl.nchunk, pl.nz);
-    } else {
-        if (!lds_limit.raise((int)ldsb, conv3x3_direct_bf16<NB, P, MODE, WX>)) return DCD_ERR_LAUNCH;
-        hipLaunchKernelGGL((conv3x3_direct_bf16<NB, P, MODE, WX>), dim3(pl.tiles_x * pl.tiles_y, B, pl.nz * pl.ksplit), dim3(DC_NT * WX), ldsb,
-                           stream, input, wd, output, part, bias, residual, Cc, H, W, Kk, pl.tiles_x, pl.nchunk, pl.nz);
-    }
-    return DCD_OK;
+    if constexpr (MODE == 2) return conv_launch<conv3x3_direct_bf16_w4<NB, P, WX>, unsigned>(c, DC_NT * WX, ldsb);
+    else return conv_launch<conv3x3_direct_bf16<NB, P, MODE, WX>, unsigned>(c, DC_NT * WX, ldsb);
 }
 
-static size_t tw_dwords_split(int Cin, int Cout, int backward_data)
+// the six instances of the direct kernel that exist per NB: 16 x 32 px regions keep the weights resident, 8 x 64 px have no such mode
+template <int NB>
+static int conv_launch_direct(const ConvCall &c, int P, int mode, int wx)
 {
-    const int Cc = backward_data ? Cout : Cin, Kk = backward_data ? Cin : Cout;
-    const int nb = Kk <= 32 ? 1 : 2;
-    return (size_t)((Cc + WS_CH - 1) / WS_CH) * ((Kk + 32 * nb - 1) / (32 * nb)) * 16 * nb * 2 * 256;
+    if (P == 4) return conv_launch_direct<NB, 4, 0, 1>(c);
+    if (wx == 2) return mode == 2 ? conv_launch_direct<NB, 2, 2, 2>(c) : conv_launch_direct<NB, 2, 1, 2>(c);
+    return mode == 2 ? conv_launch_direct<NB, 2, 2, 1>(c) : mode == 1 ? conv_launch_direct<NB, 2, 1, 1>(c) : conv_launch_direct<NB, 2, 0, 1>(c);
+}
+
+static void sum_partials(hipStream_t stream, float *output, const float *part, size_t img, int ksplit)
+{
+    if (ksplit < 2) return;
+    const size_t n4 = img / 4;                                          // W % 4 == 0
+    hipLaunchKernelGGL(wino_sum_partials, dim3(blocks256(n4, 2048)), dim3(256), 0, stream, output, part, n4, ksplit - 1);
+}
+
+// The three stride-1 forms.  weights: of this direction in the form's layout; raw_weights (fp32 form only): the untransformed
+// (Cout, Cin, 3, 3), which `launch` transforms into the head of the workspace first.  launch(call) picks the kernel instance.
+template <typename Launch>
+static int conv3x3_run(ConvForm form, void *stream, const float *input, const void *weights, bool raw_weights, const float *bias,
+                       const float *residual, float *output, int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace,
+                       size_t workspace_bytes, Launch launch)
+{
+    (void)hipGetLastError();
+    if (!input || !weights || !output || (bias && backward_data) || !conv3x3_shape_ok(form, B, Cin, H, W, Cout, backward_data))
+        return DCD_ERR_BAD_ARG;
+    const ConvDir d = conv_dir(Cin, Cout, backward_data, WN_CH);
+    ConvPlan pl = conv_plan_of(form, device_cus(), B, d.Cc, H, W, d.Kk);
+    if (const char *e = form == CONV_F32 ? dcd_env("DCD_CONV_GEOM") : nullptr) {     // A/B timing: "0" / "1" pins the region shape
+        const int g = atoi(e);
+        if (g == 0 || g == 1) {
+            pl = with_geom(pl, g, H, W);
+            pl.ksplit = 1;
+        }
+    }
+    const size_t head_floats = raw_weights ? d.wino_floats() : 0;
+    const size_t need = head_floats * sizeof(float) + pl.part_bytes();
+    if (need && (!workspace || workspace_bytes < need)) return DCD_ERR_WORKSPACE;
+    ConvCall c{(hipStream_t)stream, pl, input, weights, output, (float *)workspace + head_floats, bias, residual, B, d.Cc, H, W, d.Kk};
+    const int st = launch(c);
+    if (st != DCD_OK) return st;
+    sum_partials(c.stream, output, c.part, pl.img, pl.ksplit);
+    return launch_status();
+}
+
+static int conv3x3_f32(void *stream, const float *input, const float *weights, bool prepared, const float *bias, const float *residual,
+                       float *output, int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace, size_t workspace_bytes)
+{
+    return conv3x3_run(CONV_F32, stream, input, weights, !prepared, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
+                       workspace_bytes, [&](ConvCall &c) {
+        if (!prepared) {
+            // forward: w is (Cout, Cin, 3, 3) = (Kk, Cc); backward-data: w is (Cout, Cin) = (Cc, Kk), read transposed + flipped
+            const int ksz = 32 * c.pl.nb, nprep = c.pl.nz * c.pl.nchunk * ksz * WN_CH;
+            hipLaunchKernelGGL(wino_prep_weights, dim3(blocks256(nprep, 4096)), dim3(256), 0, c.stream, weights, (float *)workspace, c.Cc,
+                               c.Kk, backward_data ? 1 : 0, c.pl.nchunk, c.pl.nz, ksz);
+            c.weights = workspace;
+        }
+        return c.pl.geom == 0 ? (c.pl.nb == 2 ? conv_launch_f32<2, 16, 2>(c) : conv_launch_f32<2, 16, 1>(c))
+                              : (c.pl.nb == 2 ? conv_launch_f32<3, 10, 2>(c) : conv_launch_f32<3, 10, 1>(c));
+    });
+}
+
+// one launch prepares many layers' weights: blockIdx.z = table entry, blockIdx.y = direction, blocks_x blocks of 256 threads each
+template <auto Kernel>
+static int transform_weights_table(void *stream, const long long *table, int entries, int blocks_x)
+{
+    (void)hipGetLastError();
+    if (!table || entries <= 0 || entries > 65535) return DCD_ERR_BAD_ARG;
+    hipLaunchKernelGGL(Kernel, dim3(blocks_x, 2, entries), dim3(256), 0, (hipStream_t)stream, table);
+    return launch_status();
+}
+
+// ---- 1x1 convolutions of up to four concatenated inputs: the one-product form (conv1x1_bf16.inc) and exact fp32 (conv1x1_f32.inc)
+static bool pw_args(PwArgs &a, const float *weight, int ldw, int transposed, int n_inputs, const float *const *inputs, const int *channels,
+                    float *output, int B, int M, long long HW)
+{
+    if (!weight || !inputs || !channels || !output || n_inputs < 1 || n_inputs > 4 || B <= 0 || M <= 0 || HW <= 0 || (HW & 3) || ldw <= 0)
+        return false;
+    a.n_in = n_inputs;
+    a.K = 0;
+    for (int i = 0; i < 4; ++i) {
+        a.in[i] = i < n_inputs ? inputs[i] : nullptr;
+        a.ch[i] = i < n_inputs ? channels[i] : 0;
+        if (i < n_inputs && (!inputs[i] || channels[i] <= 0 || (channels[i] & 15) || (int64_t)channels[i] * HW >= (1ll << 29))) return false;
+        a.K += a.ch[i];
+    }
+    if ((int64_t)M * HW >= (1ll << 31)) return false;
+    a.w = weight; a.ldw = ldw; a.wt = transposed ? 1 : 0; a.out = output; a.M = M; a.HW = HW;
+    return true;
+}
+
+// K1 / K2: the kernel with one / two 32-channel output blocks per workgroup
+template <auto K1, auto K2>
+static int conv1x1_run(void *stream, const float *weight, int ldw, int transposed, int n_inputs, const float *const *inputs,
+                       const int *channels, float *output, int B, int M, long long HW)
+{
+    (void)hipGetLastError();
+    PwArgs a;
+    if (!pw_args(a, weight, ldw, transposed, n_inputs, inputs, channels, output, B, M, HW)) return DCD_ERR_BAD_ARG;
+    const int nb = M <= 32 ? 1 : 2;
+    hipLaunchKernelGGL(nb == 2 ? K2 : K1, dim3((unsigned)((HW + 511) / 512), B, (M + 32 * nb - 1) / (32 * nb)), dim3(PW_NT), 0,
+                       (hipStream_t)stream, a);
+    return launch_status();
+}
+
+template <int GROUP_WIDTH, int LDS_DWORDS, auto Kernel, auto Reduce>
+static int conv1x1_wrw_run(void *stream_, const float *grad_output, const float *input, float *grad_weight, int ldw, int B, int O, int C,
+                           long long HW, void *workspace, size_t workspace_bytes)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    if (!grad_output || !input || !grad_weight || !workspace || B <= 0 || O <= 0 || C <= 0 || HW <= 0 || (HW & 3) || ldw < C)
+        return DCD_ERR_BAD_ARG;
+    if ((int64_t)B * (O > C ? O : C) * HW >= (1ll << 29)) return DCD_ERR_BAD_ARG;
+    const PwWrwPartition p = pw_wrw_partition(device_cus(), B, O, C, HW, GROUP_WIDTH);
+    if (workspace_bytes < p.bytes()) return DCD_ERR_WORKSPACE;
+    const size_t ldsb = (size_t)LDS_DWORDS * 4;
+    if (!lds_ok<Kernel>(ldsb)) return DCD_ERR_LAUNCH;
+    hipLaunchKernelGGL(Kernel, dim3(p.S, p.ncg, p.nog), dim3(PWW_NT), ldsb, stream, grad_output, input, (float *)workspace, B, O, C, HW, p.S);
+    hipLaunchKernelGGL(Reduce, dim3(64, 4 * p.ncg, p.nog), dim3(256), 0, stream, (const float *)workspace, grad_weight, O, C, ldw, p.S, p.ncg);
+    return launch_status();
+}
+
+// ---- 3x3 / stride 2 / pad 1 in exact fp32 (conv_s2_f32.inc).  K2 / K4: the kernel at two / four output pixels per lane; zblocks:
+// the grid's z extent.  Four pixels per lane (512 per workgroup) unless that leaves fewer workgroups than CUs: then two (small maps).
+template <auto K2, auto K4>
+static int s2_run(void *stream, const float *x, const float *weight, float *y, int B, int Cin, int H, int W, int Cout, int zblocks)
+{
+    const S2Args a{x, weight, y, B, Cin, H, W, Cout, H / 2, W / 2};
+    const int px = a.Ho * a.Wo;
+    if ((int64_t)((px + 511) / 512) * B * zblocks < (int64_t)device_cus())
+        hipLaunchKernelGGL(K2, dim3((unsigned)((px + 255) / 256), B, zblocks), dim3(S2_NT), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(K4, dim3((unsigned)((px + 511) / 512), B, zblocks), dim3(S2_NT), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+// ---- 3x3 / stride 1 weight gradient: the Winograd kernel with NB blocks of 32 outputs per workgroup; bf = the one-product form
+template <int NB, typename Launch>
+static int wrw_wino(bool bf, Launch launch)
+{
+    const size_t ldsb = (size_t)2 * WrwGeom<NB>::BUF * sizeof(float);
+    if (!lds_ok<wino_wrw3x3_f32<NB, false>, wino_wrw3x3_f32<NB, true>>(ldsb)) return DCD_ERR_LAUNCH;
+    launch(bf ? wino_wrw3x3_f32<NB, true> : wino_wrw3x3_f32<NB, false>, WW_NT, ldsb);
+    return DCD_OK;
 }
 
 extern "C" {
 
+// ---- 3x3 / stride 1 in fp32: Winograd
 size_t dcd_conv3x3_workspace_bytes(int B, int Cin, int H, int W, int Cout)
 {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    const int cmax = Cin > Cout ? Cin : Cout;
-    const size_t nchunk = (size_t)(cmax + WN_CH - 1) / WN_CH, nz = (size_t)(cmax + 63) / 64;
     // transformed weights + the partial images of a split contraction (either direction of the call)
-    const ConvPlan f = conv_plan(B, Cin, H, W, Cout), d = conv_plan(B, Cout, H, W, Cin);
-    const size_t pf = (size_t)(f.ksplit - 1) * B * Cout * H * W, pd = (size_t)(d.ksplit - 1) * B * Cin * H * W;
-    return (nchunk * nz * 16 * 64 * WN_CH + (pf > pd ? pf : pd)) * sizeof(float);
-}
-
-// weights: raw (Cout, Cin, 3, 3) when !prepared (transformed into the head of the workspace first), else the transformed weights
-// of this direction from dcd_conv3x3_transform_weights.
-static int conv3x3_run(hipStream_t stream, const float *input, const float *weights, int prepared, const float *bias,
-                       const float *residual, float *output, int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace,
-                       size_t workspace_bytes)
-{
-    (void)hipGetLastError();
-    if (!input || !weights || !output || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DCD_ERR_BAD_ARG;
-    if ((W & 3) || (H & 1) || (int64_t)(Cin > Cout ? Cin : Cout) * H * W >= (1ll << 31) || (bias && backward_data)) return DCD_ERR_BAD_ARG;
-    // contraction channels Cc and produced channels Kk of this call
-    const int Cc = backward_data ? Cout : Cin, Kk = backward_data ? Cin : Cout;
-    ConvPlan pl = conv_plan(B, Cc, H, W, Kk);
-    if (const char *e = dcd_env("DCD_CONV_GEOM")) {                     // A/B timing: "0" / "1" pins the region shape
-        const int g = atoi(e);
-        if (g == 0 || g == 1) {
-            ConvPlan q = pl;
-            q.geom = g;
-            q.tiles_x = g == 0 ? (W + 31) / 32 : (W + 19) / 20;
-            q.tiles_y = g == 0 ? (H + 7) / 8 : (H + 11) / 12;
-            q.ksplit = 1;
-            pl = q;
-        }
-    }
-    const int ksz = 32 * pl.nb;
-    const size_t ul_floats = prepared ? 0 : (size_t)pl.nchunk * pl.nz * 16 * ksz * WN_CH;
-    const size_t img = (size_t)B * Kk * H * W;
-    const size_t need = (ul_floats + (size_t)(pl.ksplit - 1) * img) * sizeof(float);
-    if (need && (!workspace || workspace_bytes < need)) return DCD_ERR_WORKSPACE;
-    float *part = (float *)workspace + ul_floats;
-    const float *ul = weights;
-    if (!prepared) {
-        const int nprep = pl.nz * pl.nchunk * ksz * WN_CH;
-        // forward: w is (Cout, Cin, 3, 3) = (Kk, Cc); backward-data: w is (Cout, Cin) = (Cc, Kk), read transposed + flipped
-        hipLaunchKernelGGL(wino_prep_weights, dim3((nprep + 255) / 256 < 4096 ? (nprep + 255) / 256 : 4096), dim3(256), 0, stream, weights,
-                           (float *)workspace, Cc, Kk, backward_data ? 1 : 0, pl.nchunk, pl.nz, ksz);
-        ul = (const float *)workspace;
-    }
-    const int st = pl.geom == 0 ? (pl.nb == 2 ? conv_launch<2, 16, 2>(stream, pl, input, ul, output, part, bias, residual, B, Cc, H, W, Kk)
-                                              : conv_launch<2, 16, 1>(stream, pl, input, ul, output, part, bias, residual, B, Cc, H, W, Kk))
-                                : (pl.nb == 2 ? conv_launch<3, 10, 2>(stream, pl, input, ul, output, part, bias, residual, B, Cc, H, W, Kk)
-                                              : conv_launch<3, 10, 1>(stream, pl, input, ul, output, part, bias, residual, B, Cc, H, W, Kk));
-    if (st != DCD_OK) return st;
-    if (pl.ksplit > 1) {
-        const size_t n4 = img / 4;                                      // W % 4 == 0
-        const int nb = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        hipLaunchKernelGGL(wino_sum_partials, dim3(nb), dim3(256), 0, stream, output, (const float *)part, n4, pl.ksplit - 1);
-    }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    if (!conv_sizes_ok(B, Cin, H, W, Cout)) return 0;
+    return wino_floats_bound(Cin, Cout) * sizeof(float) + conv_part_bytes_either(CONV_F32, device_cus(), B, Cin, H, W, Cout);
 }
 
 int dcd_conv3x3(void *stream_, const float *input, const float *weight, const float *bias, const float *residual, float *output,
                 int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace, size_t workspace_bytes)
 {
     if (!workspace) return DCD_ERR_BAD_ARG;
-    return conv3x3_run((hipStream_t)stream_, input, weight, 0, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
-                       workspace_bytes);
-}
-
-// floats of the transformed weights of one direction (layout: the kernels' weight slab per (output slice, chunk))
-static size_t tw_floats(int Cin, int Cout, int backward_data)
-{
-    const int Cc = backward_data ? Cout : Cin, Kk = backward_data ? Cin : Cout;
-    const int nb = Kk <= 32 ? 1 : 2, ks = 32 * nb;
-    return (size_t)((Cc + WN_CH - 1) / WN_CH) * ((Kk + ks - 1) / ks) * 16 * ks * WN_CH;
+    return conv3x3_f32(stream_, input, weight, false, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace, workspace_bytes);
 }
 
 size_t dcd_conv3x3_weights_bytes(int Cin, int Cout, int backward_data)
 {
-    return Cin > 0 && Cout > 0 ? tw_floats(Cin, Cout, backward_data) * sizeof(float) : 0;
+    return Cin > 0 && Cout > 0 ? conv_dir(Cin, Cout, backward_data, WN_CH).wino_floats() * sizeof(float) : 0;
 }
 
 int dcd_conv3x3_transform_weights(void *stream_, const float *weight, int Cin, int Cout, float *forward_out, float *backward_out)
@@ -1270,43 +1264,36 @@ int dcd_conv3x3_transform_weights(void *stream_, const float *weight, int Cin, i
     (void)hipGetLastError();
     if (!weight || Cin <= 0 || Cout <= 0 || (!forward_out && !backward_out)) return DCD_ERR_BAD_ARG;
     PrepBoth p;
-    int nmax = 0;
+    size_t nmax = 0;
     for (int mode = 0; mode < 2; ++mode) {
-        const int Cc = mode ? Cout : Cin, Kk = mode ? Cin : Cout;
+        const ConvDir d = conv_dir(Cin, Cout, mode, WN_CH);
         p.ul[mode] = mode ? backward_out : forward_out;
-        p.Cc[mode] = Cc;
-        p.Kk[mode] = Kk;
-        p.ks[mode] = Kk <= 32 ? 32 : 64;
-        p.nchunk[mode] = (Cc + WN_CH - 1) / WN_CH;
-        p.nz[mode] = (Kk + p.ks[mode] - 1) / p.ks[mode];
-        const int n = p.nz[mode] * p.nchunk[mode] * p.ks[mode] * WN_CH;
+        p.Cc[mode] = d.Cc; p.Kk[mode] = d.Kk; p.ks[mode] = d.ks; p.nchunk[mode] = d.nchunk; p.nz[mode] = d.nz;
+        const size_t n = d.wino_floats() / 16;                                 // one item writes its 16 positions
         if (p.ul[mode] && n > nmax) nmax = n;
     }
-    const int nb = (nmax + 255) / 256 < 4096 ? (nmax + 255) / 256 : 4096;
-    hipLaunchKernelGGL(wino_prep_weights_both, dim3(nb, 2), dim3(256), 0, (hipStream_t)stream_, weight, p);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    hipLaunchKernelGGL(wino_prep_weights_both, dim3(blocks256(nmax, 4096), 2), dim3(256), 0, (hipStream_t)stream_, weight, p);
+    return launch_status();
 }
 
 int dcd_conv3x3_transform_weights_table(void *stream_, const long long *table, int entries)
 {
-    (void)hipGetLastError();
-    if (!table || entries <= 0 || entries > 65535) return DCD_ERR_BAD_ARG;
-    // 64 blocks x 256 threads per (layer, direction): the largest DGDE layer (512 -> 512) has 262 144 items = 16 per thread
-    hipLaunchKernelGGL(wino_prep_weights_table, dim3(64, 2, entries), dim3(256), 0, (hipStream_t)stream_, table);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    // 64 blocks per (layer, direction): the largest DGDE layer (512 -> 512) has 262 144 items = 16 per thread
+    return transform_weights_table<wino_prep_weights_table>(stream_, table, entries, 64);
 }
 
 int dcd_conv3x3_prepared(void *stream_, const float *input, const float *transformed, const float *bias, const float *residual,
                          float *output, int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace,
                          size_t workspace_bytes)
 {
-    return conv3x3_run((hipStream_t)stream_, input, transformed, 1, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
+    return conv3x3_f32(stream_, input, transformed, true, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
                        workspace_bytes);
 }
 
+// ---- the split-bf16 Winograd form (DCD_PREC_BF16X3; DCD_PREC_BF16 reads the hi halves only)
 size_t dcd_conv3x3_split_weights_bytes(int Cin, int Cout, int backward_data)
 {
-    return Cin > 0 && Cout > 0 ? tw_dwords_split(Cin, Cout, backward_data) * sizeof(unsigned) : 0;
+    return Cin > 0 && Cout > 0 ? conv_dir(Cin, Cout, backward_data, WS_CH).split_dwords() * sizeof(unsigned) : 0;
 }
 
 int dcd_conv3x3_split_transform_weights(void *stream_, const float *weight, int Cin, int Cout, void *forward_out, void *backward_out)
@@ -1317,292 +1304,131 @@ int dcd_conv3x3_split_transform_weights(void *stream_, const float *weight, int 
     for (int mode = 0; mode < 2; ++mode) {
         unsigned *dst = (unsigned *)(mode ? backward_out : forward_out);
         if (!dst) continue;
-        const int Cc = mode ? Cout : Cin, Kk = mode ? Cin : Cout;
-        const int nb = Kk <= 32 ? 1 : 2, nchunk = (Cc + WS_CH - 1) / WS_CH, nz = (Kk + 32 * nb - 1) / (32 * nb);
-        const int n = nz * nchunk * 32 * nb * 8;
-        const int grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-        if (nb == 2) hipLaunchKernelGGL(wino_prep_weights_split<2>, dim3(grid), dim3(256), 0, stream, weight, dst, Cc, Kk, mode, nchunk, nz);
-        else hipLaunchKernelGGL(wino_prep_weights_split<1>, dim3(grid), dim3(256), 0, stream, weight, dst, Cc, Kk, mode, nchunk, nz);
+        const ConvDir d = conv_dir(Cin, Cout, mode, WS_CH);
+        const dim3 grid(blocks256(d.split_dwords() / 32, 4096));               // one thread writes 16 positions x (hi, lo)
+        hipLaunchKernelGGL(d.nb == 2 ? wino_prep_weights_split<2> : wino_prep_weights_split<1>, grid, dim3(256), 0, stream, weight, dst,
+                           d.Cc, d.Kk, mode, d.nchunk, d.nz);
     }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return launch_status();
 }
 
 int dcd_conv3x3_split_transform_weights_table(void *stream_, const long long *table, int entries)
 {
-    (void)hipGetLastError();
-    if (!table || entries <= 0 || entries > 65535) return DCD_ERR_BAD_ARG;
-    // 64 blocks x 256 threads per (layer, direction): the largest DGDE layer (512 -> 512) has 65 536 items of 32 stores each
-    hipLaunchKernelGGL(wino_prep_weights_split_table, dim3(64, 2, entries), dim3(256), 0, (hipStream_t)stream_, table);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    // 64 blocks per (layer, direction): the largest DGDE layer (512 -> 512) has 65 536 items of 32 stores each
+    return transform_weights_table<wino_prep_weights_split_table>(stream_, table, entries, 64);
 }
 
 size_t dcd_conv3x3_split_workspace_bytes(int B, int Cin, int H, int W, int Cout)
 {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    const ConvPlan f = conv_plan_split(B, Cin, H, W, Cout), d = conv_plan_split(B, Cout, H, W, Cin);
-    const size_t pf = (size_t)(f.ksplit - 1) * B * Cout * H * W, pd = (size_t)(d.ksplit - 1) * B * Cin * H * W;
-    return (pf > pd ? pf : pd) * sizeof(float) + 16;
+    return conv_sizes_ok(B, Cin, H, W, Cout) ? conv_part_bytes_either(CONV_SPLIT, device_cus(), B, Cin, H, W, Cout) + 16 : 0;
 }
 
 int dcd_conv3x3_split_prepared(void *stream_, const float *input, const void *transformed, const float *bias, const float *residual,
                                float *output, int B, int Cin, int H, int W, int Cout, int backward_data, int precision, void *workspace,
                                size_t workspace_bytes)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    if (!input || !transformed || !output || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DCD_ERR_BAD_ARG;
     if (precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
     const bool one = precision == DCD_PREC_BF16;
-    if ((W & 3) || (H & 1) || (int64_t)(Cin > Cout ? Cin : Cout) * H * W >= (1ll << 31) || (bias && backward_data)) return DCD_ERR_BAD_ARG;
-    const int Cc = backward_data ? Cout : Cin, Kk = backward_data ? Cin : Cout;
-    const ConvPlan pl = conv_plan_split(B, Cc, H, W, Kk);
-    const size_t img = (size_t)B * Kk * H * W;
-    const size_t need = (size_t)(pl.ksplit - 1) * img * sizeof(float);
-    if (need && (!workspace || workspace_bytes < need)) return DCD_ERR_WORKSPACE;
-    float *part = (float *)workspace;
-    const unsigned *us = (const unsigned *)transformed;
-    const int st = pl.nb == 2 ? (one ? conv_launch_split<2, 1>(stream, pl, input, us, output, part, bias, residual, B, Cc, H, W, Kk)
-                                     : conv_launch_split<2, 3>(stream, pl, input, us, output, part, bias, residual, B, Cc, H, W, Kk))
-                              : (one ? conv_launch_split<1, 1>(stream, pl, input, us, output, part, bias, residual, B, Cc, H, W, Kk)
-                                     : conv_launch_split<1, 3>(stream, pl, input, us, output, part, bias, residual, B, Cc, H, W, Kk));
-    if (st != DCD_OK) return st;
-    if (pl.ksplit > 1) {
-        const size_t n4 = img / 4;
-        const int nb = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        hipLaunchKernelGGL(wino_sum_partials, dim3(nb), dim3(256), 0, stream, output, (const float *)part, n4, pl.ksplit - 1);
-    }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return conv3x3_run(CONV_SPLIT, stream_, input, transformed, false, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
+                       workspace_bytes, [one](ConvCall &c) {
+        return c.pl.nb == 2 ? (one ? conv_launch_split<2, 1>(c) : conv_launch_split<2, 3>(c))
+                            : (one ? conv_launch_split<1, 1>(c) : conv_launch_split<1, 3>(c));
+    });
 }
 
 // ---- the one-product form as a direct implicit GEMM (conv_direct_bf16.inc): its own weight layout, same call shape
 size_t dcd_conv3x3_bf16_weights_bytes(int Cin, int Cout, int backward_data)
 {
     if (Cin <= 0 || Cout <= 0) return 0;
-    return 16 * (backward_data ? dc_weight_slots(Cout, Cin) : dc_weight_slots(Cin, Cout));
+    const ConvDir d = conv_dir(Cin, Cout, backward_data, DC_CH);
+    return 16 * dc_weight_slots(d.Cc, d.Kk);
 }
 
 int dcd_conv3x3_bf16_transform_weights(void *stream_, const float *weight, int Cin, int Cout, void *forward_out, void *backward_out)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     if (!weight || Cin <= 0 || Cout <= 0 || (!forward_out && !backward_out)) return DCD_ERR_BAD_ARG;
     DirectPrep p;
     size_t nmax = 0;
     for (int mode = 0; mode < 2; ++mode) {
+        const ConvDir d = conv_dir(Cin, Cout, mode, DC_CH);
         p.ud[mode] = (unsigned *)(mode ? backward_out : forward_out);
-        p.Cc[mode] = mode ? Cout : Cin;
-        p.Kk[mode] = mode ? Cin : Cout;
+        p.Cc[mode] = d.Cc; p.Kk[mode] = d.Kk;
         const size_t n = p.ud[mode] ? dc_weight_slots(p.Cc[mode], p.Kk[mode]) : 0;
         if (n > nmax) nmax = n;
     }
-    nmax /= 9;                                                             // one thread per nine slots
-    const int nb = (int)((nmax + 255) / 256 < 2048 ? (nmax + 255) / 256 : 2048);
-    hipLaunchKernelGGL(direct_prep_weights_both, dim3(nb, 2), dim3(256), 0, stream, weight, p);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    // one thread per nine slots
+    hipLaunchKernelGGL(direct_prep_weights_both, dim3(blocks256(nmax / 9, 2048), 2), dim3(256), 0, (hipStream_t)stream_, weight, p);
+    return launch_status();
 }
 
 int dcd_conv3x3_bf16_transform_weights_table(void *stream_, const long long *table, int entries)
 {
-    (void)hipGetLastError();
-    if (!table || entries <= 0 || entries > 65535) return DCD_ERR_BAD_ARG;
-    // 32 blocks x 256 threads per (layer, direction): the largest DGDE layer (512 -> 512) has 16 384 items of nine slots = 2 per thread
-    hipLaunchKernelGGL(direct_prep_weights_table, dim3(32, 2, entries), dim3(256), 0, (hipStream_t)stream_, table);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    // 32 blocks per (layer, direction): the largest DGDE layer (512 -> 512) has 16 384 items of nine slots = 2 per thread
+    return transform_weights_table<direct_prep_weights_table>(stream_, table, entries, 32);
 }
 
 size_t dcd_conv3x3_bf16_workspace_bytes(int B, int Cin, int H, int W, int Cout)
 {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t pf = (size_t)(conv_plan_direct(B, Cin, H, W, Cout).ksplit - 1) * B * Cout * H * W;
-    const size_t pd = (size_t)(conv_plan_direct(B, Cout, H, W, Cin).ksplit - 1) * B * Cin * H * W;
-    return (pf > pd ? pf : pd) * sizeof(float) + 16;
+    return conv_sizes_ok(B, Cin, H, W, Cout) ? conv_part_bytes_either(CONV_DIRECT, device_cus(), B, Cin, H, W, Cout) + 16 : 0;
 }
 
 int dcd_conv3x3_bf16_prepared(void *stream_, const float *input, const void *transformed, const float *bias, const float *residual,
                               float *output, int B, int Cin, int H, int W, int Cout, int backward_data, void *workspace,
                               size_t workspace_bytes)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    if (!input || !transformed || !output || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DCD_ERR_BAD_ARG;
-    if (bias && backward_data) return DCD_ERR_BAD_ARG;
-    const int Cc = backward_data ? Cout : Cin, Kk = backward_data ? Cin : Cout;
-    if (!conv_direct_ok(Cc, H, W) || (int64_t)Kk * H * W >= (1ll << 31) || (W & 3)) return DCD_ERR_BAD_ARG;
-    const ConvPlan pl = conv_plan_direct(B, Cc, H, W, Kk);
-    const size_t img = (size_t)B * Kk * H * W;
-    const size_t need = (size_t)(pl.ksplit - 1) * img * sizeof(float);
-    if (need && (!workspace || workspace_bytes < need)) return DCD_ERR_WORKSPACE;
-    if (pl.ksplit > 1 && (img & 3)) return DCD_ERR_BAD_ARG;               // wino_sum_partials adds float4s
-    float *part = (float *)workspace;
-    const unsigned *wd = (const unsigned *)transformed;
-    // DCD_CONV_DIRECT_MODE: 0 weights resident, 1 window resident, 2 both streamed (default: 2 with 8 x 64 regions, else 1)
-    static const int mpin = dcd_env("DCD_CONV_DIRECT_MODE") ? atoi(dcd_env("DCD_CONV_DIRECT_MODE")) : -1;
-    const int P = pl.geom & 15, wx = pl.geom >> 4;
-    const int mode = P == 4 ? 0 : (mpin >= 0 ? mpin : 1);
-#define DCD_DIRECT(NB_, P_, M_, WX_) conv_launch_direct<NB_, P_, M_, WX_>(stream, pl, input, wd, output, part, bias, residual, B, Cc, H, W, Kk)
-#define DCD_DIRECT_NB(NB_)                                                                                                              \
-    (P == 4 ? DCD_DIRECT(NB_, 4, 0, 1)                                                                                                  \
-            : wx == 2 ? (mode == 2 ? DCD_DIRECT(NB_, 2, 2, 2) : DCD_DIRECT(NB_, 2, 1, 2))                                               \
-                      : (mode == 2 ? DCD_DIRECT(NB_, 2, 2, 1) : mode == 1 ? DCD_DIRECT(NB_, 2, 1, 1) : DCD_DIRECT(NB_, 2, 0, 1)))
-    const int st = pl.nb == 2 ? DCD_DIRECT_NB(2) : DCD_DIRECT_NB(1);
-#undef DCD_DIRECT_NB
-#undef DCD_DIRECT
-    if (st != DCD_OK) return st;
-    if (pl.ksplit > 1) {
-        const size_t n4 = img / 4;
-        const int nb = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        hipLaunchKernelGGL(wino_sum_partials, dim3(nb), dim3(256), 0, stream, output, (const float *)part, n4, pl.ksplit - 1);
-    }
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return conv3x3_run(CONV_DIRECT, stream_, input, transformed, false, bias, residual, output, B, Cin, H, W, Cout, backward_data, workspace,
+                       workspace_bytes, [](ConvCall &c) {
+        // DCD_CONV_DIRECT_MODE: 0 weights resident, 1 window resident, 2 both streamed (default 1)
+        static const int mpin = dcd_env("DCD_CONV_DIRECT_MODE") ? atoi(dcd_env("DCD_CONV_DIRECT_MODE")) : -1;
+        const int P = c.pl.geom & 15, wx = c.pl.geom >> 4, mode = mpin >= 0 ? mpin : 1;
+        return c.pl.nb == 2 ? conv_launch_direct<2>(c, P, mode, wx) : conv_launch_direct<1>(c, P, mode, wx);
+    });
 }
 
-// ---- 1x1 convolutions in the one-product form (conv1x1_bf16.inc)
+// ---- 1x1 convolutions: the one-product form and exact fp32
 int dcd_conv1x1_bf16(void *stream_, const float *weight, int ldw, int transposed, int n_inputs, const float *const *inputs,
                      const int *channels, float *output, int B, int M, long long HW)
 {
-    (void)hipGetLastError();
-    if (!weight || !inputs || !channels || !output || n_inputs < 1 || n_inputs > 4 || B <= 0 || M <= 0 || HW <= 0 || (HW & 3) || ldw <= 0)
-        return DCD_ERR_BAD_ARG;
-    PwArgs a;
-    a.n_in = n_inputs;
-    a.K = 0;
-    for (int i = 0; i < 4; ++i) {
-        a.in[i] = i < n_inputs ? inputs[i] : nullptr;
-        a.ch[i] = i < n_inputs ? channels[i] : 0;
-        if (i < n_inputs && (!inputs[i] || channels[i] <= 0 || (channels[i] & 15) || (int64_t)channels[i] * HW >= (1ll << 29)))
-            return DCD_ERR_BAD_ARG;
-        a.K += a.ch[i];
-    }
-    if ((int64_t)M * HW >= (1ll << 31)) return DCD_ERR_BAD_ARG;
-    a.w = weight; a.ldw = ldw; a.wt = transposed ? 1 : 0; a.out = output; a.M = M; a.HW = HW;
-    const int nb = M <= 32 ? 1 : 2;
-    dim3 grid((unsigned)((HW + 511) / 512), B, (M + 32 * nb - 1) / (32 * nb));
-    if (nb == 2) hipLaunchKernelGGL(pw_conv_bf16<2>, grid, dim3(PW_NT), 0, (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL(pw_conv_bf16<1>, grid, dim3(PW_NT), 0, (hipStream_t)stream_, a);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return conv1x1_run<pw_conv_bf16<1>, pw_conv_bf16<2>>(stream_, weight, ldw, transposed, n_inputs, inputs, channels, output, B, M, HW);
 }
 
-static void pw_wrw_partition(int B, int O, int C, long long HW, int &nog, int &ncg, int &S)
+int dcd_conv1x1_f32(void *stream_, const float *weight, int ldw, int transposed, int n_inputs, const float *const *inputs,
+                    const int *channels, float *output, int B, int M, long long HW)
 {
-    nog = (O + 63) / 64;
-    ncg = (C + 127) / 128;
-    const int64_t T = (int64_t)B * ((HW + 63) / 64);
-    int64_t s = 2 * (int64_t)device_cus() / (nog * ncg);           // two workgroups per CU
-    if (s > T / 4) s = T / 4;
-    if (s < 1) s = 1;
-    S = (int)s;
+    return conv1x1_run<pw_conv_f32<1>, pw_conv_f32<2>>(stream_, weight, ldw, transposed, n_inputs, inputs, channels, output, B, M, HW);
 }
 
 size_t dcd_conv1x1_wrw_bf16_workspace_bytes(int B, int O, int C, long long HW)
 {
-    if (B <= 0 || O <= 0 || C <= 0 || HW <= 0) return 0;
-    int nog, ncg, S;
-    pw_wrw_partition(B, O, C, HW, nog, ncg, S);
-    return (size_t)nog * ncg * S * 64 * 128 * sizeof(float);
+    return B > 0 && O > 0 && C > 0 && HW > 0 ? pw_wrw_partition(device_cus(), B, O, C, HW, 128).bytes() : 0;
 }
 
 int dcd_conv1x1_wrw_bf16(void *stream_, const float *grad_output, const float *input, float *grad_weight, int ldw, int B, int O, int C,
                          long long HW, void *workspace, size_t workspace_bytes)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    if (!grad_output || !input || !grad_weight || !workspace || B <= 0 || O <= 0 || C <= 0 || HW <= 0 || (HW & 3) || ldw < C)
-        return DCD_ERR_BAD_ARG;
-    if ((int64_t)B * (O > C ? O : C) * HW >= (1ll << 29)) return DCD_ERR_BAD_ARG;
-    int nog, ncg, S;
-    pw_wrw_partition(B, O, C, HW, nog, ncg, S);
-    if (workspace_bytes < (size_t)nog * ncg * S * 64 * 128 * sizeof(float)) return DCD_ERR_WORKSPACE;
-    static LdsLimit lds_limit;
-    const size_t ldsb = (size_t)PWW_LDS * sizeof(unsigned);
-    if (!lds_limit.raise((int)ldsb, pw_wrw_bf16)) return DCD_ERR_LAUNCH;
-    hipLaunchKernelGGL(pw_wrw_bf16, dim3(S, ncg, nog), dim3(PWW_NT), ldsb, stream, grad_output, input, (float *)workspace, B, O, C, HW, S);
-    hipLaunchKernelGGL(pw_wrw_reduce, dim3(64, 4 * ncg, nog), dim3(256), 0, stream, (const float *)workspace, grad_weight, O, C, ldw, S, ncg);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-}
-
-// ---- the same layers in exact fp32 (conv1x1_f32.inc)
-int dcd_conv1x1_f32(void *stream_, const float *weight, int ldw, int transposed, int n_inputs, const float *const *inputs,
-                    const int *channels, float *output, int B, int M, long long HW)
-{
-    (void)hipGetLastError();
-    if (!weight || !inputs || !channels || !output || n_inputs < 1 || n_inputs > 4 || B <= 0 || M <= 0 || HW <= 0 || (HW & 3) || ldw <= 0)
-        return DCD_ERR_BAD_ARG;
-    PwArgs a;
-    a.n_in = n_inputs;
-    a.K = 0;
-    for (int i = 0; i < 4; ++i) {
-        a.in[i] = i < n_inputs ? inputs[i] : nullptr;
-        a.ch[i] = i < n_inputs ? channels[i] : 0;
-        if (i < n_inputs && (!inputs[i] || channels[i] <= 0 || (channels[i] & 15) || (int64_t)channels[i] * HW >= (1ll << 29)))
-            return DCD_ERR_BAD_ARG;
-        a.K += a.ch[i];
-    }
-    if ((int64_t)M * HW >= (1ll << 31)) return DCD_ERR_BAD_ARG;
-    a.w = weight; a.ldw = ldw; a.wt = transposed ? 1 : 0; a.out = output; a.M = M; a.HW = HW;
-    const int nb = M <= 32 ? 1 : 2;
-    dim3 grid((unsigned)((HW + 511) / 512), B, (M + 32 * nb - 1) / (32 * nb));
-    if (nb == 2) hipLaunchKernelGGL(pw_conv_f32<2>, grid, dim3(PW_NT), 0, (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL(pw_conv_f32<1>, grid, dim3(PW_NT), 0, (hipStream_t)stream_, a);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-}
-
-static void pw_wrw_f32_partition(int B, int O, int C, long long HW, int &nog, int &ncg, int &S)
-{
-    nog = (O + 63) / 64;
-    ncg = (C + 63) / 64;
-    const int64_t T = (int64_t)B * ((HW + 63) / 64);
-    int64_t s = 2 * (int64_t)device_cus() / (nog * ncg);           // two workgroups per CU
-    if (s > T / 4) s = T / 4;
-    if (s < 1) s = 1;
-    S = (int)s;
+    return conv1x1_wrw_run<128, PWW_LDS, pw_wrw_bf16, pw_wrw_reduce>(stream_, grad_output, input, grad_weight, ldw, B, O, C, HW, workspace,
+                                                                     workspace_bytes);
 }
 
 size_t dcd_conv1x1_wrw_f32_workspace_bytes(int B, int O, int C, long long HW)
 {
-    if (B <= 0 || O <= 0 || C <= 0 || HW <= 0) return 0;
-    int nog, ncg, S;
-    pw_wrw_f32_partition(B, O, C, HW, nog, ncg, S);
-    return (size_t)nog * ncg * S * 64 * 64 * sizeof(float);
+    return B > 0 && O > 0 && C > 0 && HW > 0 ? pw_wrw_partition(device_cus(), B, O, C, HW, 64).bytes() : 0;
 }
 
 int dcd_conv1x1_wrw_f32(void *stream_, const float *grad_output, const float *input, float *grad_weight, int ldw, int B, int O, int C,
                         long long HW, void *workspace, size_t workspace_bytes)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    if (!grad_output || !input || !grad_weight || !workspace || B <= 0 || O <= 0 || C <= 0 || HW <= 0 || (HW & 3) || ldw < C)
-        return DCD_ERR_BAD_ARG;
-    if ((int64_t)B * (O > C ? O : C) * HW >= (1ll << 29)) return DCD_ERR_BAD_ARG;
-    int nog, ncg, S;
-    pw_wrw_f32_partition(B, O, C, HW, nog, ncg, S);
-    if (workspace_bytes < (size_t)nog * ncg * S * 64 * 64 * sizeof(float)) return DCD_ERR_WORKSPACE;
-    static LdsLimit lds_limit;
-    const size_t ldsb = (size_t)PWWF_LDS * sizeof(float);
-    if (!lds_limit.raise((int)ldsb, pw_wrw_f32)) return DCD_ERR_LAUNCH;
-    hipLaunchKernelGGL(pw_wrw_f32, dim3(S, ncg, nog), dim3(PWW_NT), ldsb, stream, grad_output, input, (float *)workspace, B, O, C, HW, S);
-    hipLaunchKernelGGL(pw_wrw_reduce_f32, dim3(64, 4 * ncg, nog), dim3(256), 0, stream, (const float *)workspace, grad_weight, O, C, ldw, S, ncg);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return conv1x1_wrw_run<64, PWWF_LDS, pw_wrw_f32, pw_wrw_reduce_f32>(stream_, grad_output, input, grad_weight, ldw, B, O, C, HW,
+                                                                        workspace, workspace_bytes);
 }
 
-// ---- 3x3 / stride 2 / pad 1 in exact fp32 (conv_s2_f32.inc)
-static bool s2_args_ok(int B, int Cin, int H, int W, int Cout)
-{
-    return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (H & 1) == 0 && (W & 7) == 0 && (Cin & 15) == 0 &&
-           (int64_t)Cin * H * W < (1ll << 29) && (int64_t)Cout * (H / 2) * (W / 2) < (1ll << 29);
-}
-
+// ---- 3x3 / stride 2 / pad 1 in exact fp32
 int dcd_conv3x3_s2_f32(void *stream_, const float *input, const float *weight, float *output, int B, int Cin, int H, int W, int Cout)
 {
     (void)hipGetLastError();
     if (!input || !weight || !output || !s2_args_ok(B, Cin, H, W, Cout)) return DCD_ERR_BAD_ARG;
-    S2Args a;
-    a.x = input; a.w = weight; a.y = output; a.B = B; a.C = Cin; a.H = H; a.W = W; a.K = Cout; a.Ho = H / 2; a.Wo = W / 2;
-    // four output pixels per lane (512 per workgroup) unless that leaves fewer workgroups than CUs: then two (the small maps)
-    const int zb = (Cout + 31) / 32;
-    const bool small = (int64_t)((a.Ho * a.Wo + 511) / 512) * B * zb < (int64_t)device_cus();
-    if (small) hipLaunchKernelGGL(s2_conv_f32<2>, dim3((unsigned)((a.Ho * a.Wo + 255) / 256), B, zb), dim3(S2_NT), 0, (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL(s2_conv_f32<4>, dim3((unsigned)((a.Ho * a.Wo + 511) / 512), B, zb), dim3(S2_NT), 0, (hipStream_t)stream_, a);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return s2_run<s2_conv_f32<2>, s2_conv_f32<4>>(stream_, input, weight, output, B, Cin, H, W, Cout, (Cout + 31) / 32);
 }
 
 int dcd_conv3x3_s2_f32_backward_data(void *stream_, const float *grad_output, const float *weight, float *grad_input, int B, int Cin, int H,
@@ -1610,29 +1436,12 @@ int dcd_conv3x3_s2_f32_backward_data(void *stream_, const float *grad_output, co
 {
     (void)hipGetLastError();
     if (!grad_output || !weight || !grad_input || !s2_args_ok(B, Cin, H, W, Cout) || (Cout & 15)) return DCD_ERR_BAD_ARG;
-    S2Args a;
-    a.x = grad_output; a.w = weight; a.y = grad_input; a.B = B; a.C = Cin; a.H = H; a.W = W; a.K = Cout; a.Ho = H / 2; a.Wo = W / 2;
-    const int zb = (Cin + 31) / 32;
-    const bool small = (int64_t)((a.Ho * a.Wo + 511) / 512) * B * 2 * zb < (int64_t)device_cus();
-    if (small) hipLaunchKernelGGL(s2_dgrad_f32<2>, dim3((unsigned)((a.Ho * a.Wo + 255) / 256), B, 2 * zb), dim3(S2_NT), 0, (hipStream_t)stream_, a);
-    else hipLaunchKernelGGL(s2_dgrad_f32<4>, dim3((unsigned)((a.Ho * a.Wo + 511) / 512), B, 2 * zb), dim3(S2_NT), 0, (hipStream_t)stream_, a);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
-}
-
-static int s2_wrw_splits(int B, int Cin, int H, int W, int Cout)
-{
-    const int nblk = ((Cout + 31) / 32) * ((Cin + 31) / 32);
-    const int64_t groups = (int64_t)B * (H / 2) * (W / 2) / 8;
-    int64_t S = (8 * (int64_t)device_cus() + nblk - 1) / nblk;       // two waves per SIMD over the chip
-    if (S > groups / 8) S = groups / 8;                               // at least eight iterations per wave
-    if (S < 1) S = 1;
-    return (int)S;
+    return s2_run<s2_dgrad_f32<2>, s2_dgrad_f32<4>>(stream_, grad_output, weight, grad_input, B, Cin, H, W, Cout, 2 * ((Cin + 31) / 32));
 }
 
 size_t dcd_conv3x3_s2_f32_wrw_workspace_bytes(int B, int Cin, int H, int W, int Cout)
 {
-    if (!s2_args_ok(B, Cin, H, W, Cout)) return 0;
-    return (size_t)s2_wrw_splits(B, Cin, H, W, Cout) * 9 * Cout * Cin * sizeof(float);
+    return s2_args_ok(B, Cin, H, W, Cout) ? s2_wrw_splits(device_cus(), B, Cin, H, W, Cout).bytes() : 0;
 }
 
 int dcd_conv3x3_s2_f32_wrw(void *stream_, const float *input, const float *grad_output, float *grad_weight, int B, int Cin, int H, int W,
@@ -1642,40 +1451,20 @@ int dcd_conv3x3_s2_f32_wrw(void *stream_, const float *input, const float *grad_
     (void)hipGetLastError();
     if (!input || !grad_output || !grad_weight || !workspace || !s2_args_ok(B, Cin, H, W, Cout) || ((H / 2) & 1) || W < 16) return DCD_ERR_BAD_ARG;
     if ((int64_t)B * (Cin > Cout ? (int64_t)Cin * H * W : (int64_t)Cout * (H / 2) * (W / 2)) >= (1ll << 29)) return DCD_ERR_BAD_ARG;
-    S2WrwArgs a;
-    a.x = input; a.gy = grad_output; a.part = (float *)workspace; a.B = B; a.C = Cin; a.H = H; a.W = W; a.K = Cout; a.Ho = H / 2; a.Wo = W / 2;
-    a.S = s2_wrw_splits(B, Cin, H, W, Cout);
-    a.ncb = (Cin + 31) / 32;
-    if (workspace_bytes < (size_t)a.S * 9 * Cout * Cin * sizeof(float)) return DCD_ERR_WORKSPACE;
+    const S2WrwSplits sp = s2_wrw_splits(device_cus(), B, Cin, H, W, Cout);
+    if (workspace_bytes < sp.bytes()) return DCD_ERR_WORKSPACE;
+    const S2WrwArgs a{input, grad_output, (float *)workspace, B, Cin, H, W, Cout, H / 2, W / 2, sp.S, (Cin + 31) / 32};
     const int items = ((Cout + 31) / 32) * a.ncb * a.S;
     hipLaunchKernelGGL(s2_wrw_f32, dim3((items + 3) / 4), dim3(S2_NT), 0, stream, a);
     const int n = 9 * Cout * Cin;
     hipLaunchKernelGGL(s2_wrw_reduce, dim3((n + 15) / 16), dim3(256), 0, stream, (const float *)workspace, grad_weight, Cout, Cin, a.S);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    return launch_status();
 }
 
-static void wrw_partition(int B, int Cin, int H, int W, int Cout, int &nog, int &ncg, int &S, int &strips_x, int &KO)
-{
-    KO = Cout <= 32 ? 32 : 64;
-    nog = (Cout + KO - 1) / KO;
-    ncg = (Cin + 63) / 64;
-    strips_x = (W + 31) / 32;
-    const int T = B * (H / 2) * strips_x;
-    S = 256 / (nog * ncg);                        // about one workgroup per CU
-    // ... but at least four strips per workgroup: every split writes a 16 x 64 x 64 partial (67 MB for 256 of them) that the
-    // reduce kernel reads back, which at one image per GPU cost more than the product itself (29 + 17 us at 64 -> 64 @ 96x320)
-    if (S > T / 4) S = T / 4;
-    if (S >= 8) S &= ~7;
-    if (S < 1) S = 1;
-    if (S > T) S = T;
-}
-
+// ---- 3x3 / stride 1 weight gradient
 size_t dcd_conv3x3_wrw_workspace_bytes(int B, int Cin, int H, int W, int Cout)
 {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-    int nog, ncg, S, sx, KO;
-    wrw_partition(B, Cin, H, W, Cout, nog, ncg, S, sx, KO);
-    return (size_t)nog * ncg * S * 12 * KO * 64 * sizeof(float);
+    return conv_sizes_ok(B, Cin, H, W, Cout) ? wrw_partition(B, Cin, H, W, Cout).bytes() : 0;
 }
 
 int dcd_conv3x3_wrw(void *stream_, const float *input, const float *grad_output, float *grad_weight, int B, int Cin, int H, int W,
@@ -1683,50 +1472,33 @@ int dcd_conv3x3_wrw(void *stream_, const float *input, const float *grad_output,
 {
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (!input || !grad_output || !grad_weight || !workspace || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DCD_ERR_BAD_ARG;
+    if (!input || !grad_output || !grad_weight || !workspace) return DCD_ERR_BAD_ARG;
     if (precision != DCD_PREC_F32 && precision != DCD_PREC_BF16X3 && precision != DCD_PREC_BF16) return DCD_ERR_BAD_ARG;
     const bool bf = precision == DCD_PREC_BF16;              // the split-bf16 form has no variant of this kernel: it runs exact fp32
-    if ((W & 3) || (H & 1) || (int64_t)(Cin > Cout ? Cin : Cout) * H * W >= (1ll << 31)) return DCD_ERR_BAD_ARG;
-    int nog, ncg, S, strips_x, KO;
-    wrw_partition(B, Cin, H, W, Cout, nog, ncg, S, strips_x, KO);
-    const int nblk = nog * ncg;
-    if (workspace_bytes < (size_t)nblk * S * 12 * KO * 64 * sizeof(float)) return DCD_ERR_WORKSPACE;
+    if (!conv3x3_shape_ok(CONV_F32, B, Cin, H, W, Cout, 0)) return DCD_ERR_BAD_ARG;
+    const WrwPartition p = wrw_partition(B, Cin, H, W, Cout);
+    const int nblk = p.nblk();
+    if (workspace_bytes < p.bytes()) return DCD_ERR_WORKSPACE;
+    // all three kernels take the same partition, workspace and arguments
+    auto launch = [&](auto kernel, int threads, size_t ldsb) {
+        hipLaunchKernelGGL(kernel, dim3(nblk * p.S), dim3(threads), ldsb, stream, input, grad_output, (float *)workspace, Cin, Cout, B, H, W,
+                           p.strips_x, p.S, p.ncg, nblk);
+    };
     static const bool wrw_direct = !(dcd_env("DCD_CONV_WRW_DIRECT") && atoi(dcd_env("DCD_CONV_WRW_DIRECT")) == 0);
-    if (bf && KO == 64 && wrw_direct && (int64_t)B * (Cin > Cout ? Cin : Cout) * H * W < (1ll << 29)) {
-        // one-product form, more than 32 outputs: the direct kernel (conv_direct_bf16.inc), same partition and workspace
-        static LdsLimit lds_limit;
+    if (bf && p.KO == 64 && wrw_direct && (int64_t)B * (Cin > Cout ? Cin : Cout) * H * W < (1ll << 29)) {
+        // one-product form, more than 32 outputs: the direct kernel (conv_direct_bf16.inc)
         const size_t ldsb = (size_t)DW_LDS * sizeof(unsigned);
-        if (!lds_limit.raise((int)ldsb, conv3x3_wrw_direct_bf16)) return DCD_ERR_LAUNCH;
-        hipLaunchKernelGGL(conv3x3_wrw_direct_bf16, dim3(nblk * S), dim3(DW_NT), ldsb, stream, input, grad_output, (float *)workspace, Cin,
-                           Cout, B, H, W, strips_x, S, ncg, nblk);
+        if (!lds_ok<conv3x3_wrw_direct_bf16>(ldsb)) return DCD_ERR_LAUNCH;
+        launch(conv3x3_wrw_direct_bf16, DW_NT, ldsb);
         hipLaunchKernelGGL(conv3x3_wrw_direct_reduce, dim3(64, 3, nblk), dim3(256), 0, stream, (const float *)workspace, grad_weight, Cin, Cout,
-                           S, ncg);
-        return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+                           p.S, p.ncg);
+        return launch_status();
     }
-    if (KO == 64) {
-        static LdsLimit lds_limit;
-        const size_t ldsb = (size_t)2 * WrwGeom<2>::BUF * sizeof(float);
-        if (!lds_limit.raise((int)ldsb, wino_wrw3x3_f32<2, false>, wino_wrw3x3_f32<2, true>)) return DCD_ERR_LAUNCH;
-        if (bf)
-            hipLaunchKernelGGL((wino_wrw3x3_f32<2, true>), dim3(nblk * S), dim3(WW_NT), ldsb, stream, input, grad_output, (float *)workspace,
-                               Cin, Cout, B, H, W, strips_x, S, ncg, nblk);
-        else
-            hipLaunchKernelGGL((wino_wrw3x3_f32<2, false>), dim3(nblk * S), dim3(WW_NT), ldsb, stream, input, grad_output, (float *)workspace,
-                               Cin, Cout, B, H, W, strips_x, S, ncg, nblk);
-    } else {
-        static LdsLimit lds_limit;
-        const size_t ldsb = (size_t)2 * WrwGeom<1>::BUF * sizeof(float);
-        if (!lds_limit.raise((int)ldsb, wino_wrw3x3_f32<1, false>, wino_wrw3x3_f32<1, true>)) return DCD_ERR_LAUNCH;
-        if (bf)
-            hipLaunchKernelGGL((wino_wrw3x3_f32<1, true>), dim3(nblk * S), dim3(WW_NT), ldsb, stream, input, grad_output, (float *)workspace,
-                               Cin, Cout, B, H, W, strips_x, S, ncg, nblk);
-        else
-            hipLaunchKernelGGL((wino_wrw3x3_f32<1, false>), dim3(nblk * S), dim3(WW_NT), ldsb, stream, input, grad_output, (float *)workspace,
-                               Cin, Cout, B, H, W, strips_x, S, ncg, nblk);
-    }
-    hipLaunchKernelGGL(wino_wrw_reduce, dim3(nblk * KO * 64 / 16), dim3(256), 0, stream, (const float *)workspace, grad_weight, Cin, Cout,
-                       S, ncg, KO);
-    return hipGetLastError() == hipSuccess ? DCD_OK : DCD_ERR_LAUNCH;
+    const int st = p.KO == 64 ? wrw_wino<2>(bf, launch) : wrw_wino<1>(bf, launch);
+    if (st != DCD_OK) return st;
+    hipLaunchKernelGGL(wino_wrw_reduce, dim3(nblk * p.KO * 64 / 16), dim3(256), 0, stream, (const float *)workspace, grad_weight, Cin, Cout,
+                       p.S, p.ncg, p.KO);
+    return launch_status();
 }
 
 }  // extern "C"

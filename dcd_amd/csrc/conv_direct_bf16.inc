@@ -23,7 +23,6 @@
 // end returns zero (so does the out-of-image sentinel 0x7ffffff0 + anything below 2^31).  Requires (Cc + 16) H W < 2^29.
 
 constexpr int DC_NT = 256;
-constexpr int DC_CH = 16;
 constexpr int DC_OOB = 0x7ffffff0;
 
 // 16-byte slots of the direct-layout weights of one direction
