@@ -1,5 +1,5 @@
-"""Shared by test_eval_host.py and test_gpu_eval.py: loaders for the evaluator fixtures of tests/golden/make_golden_eval.py,
-and a numpy stand-in for the device evaluator (test-only: the product has no CPU path)."""
+"""Shared by test_eval_host.py, test_gpu_eval.py and test_gpu_eval_ties.py: loaders for the evaluator fixtures of
+tests/golden/make_golden_eval.py and make_golden_eval_ties.py, and a numpy stand-in for the device evaluator (test-only: the product has no CPU path)."""
 import functools
 import math
 import os
@@ -167,3 +167,93 @@ class EmulatedEvaluator:
                     if slot >= 0:
                         sim[slot, t] += s
         return counts, sim
+
+
+# ---- the tie fixture of tests/golden/make_golden_eval_ties.py ---------------------------------------------------------------
+TIES_SCENE_DIR = os.path.join(GOLDEN, "eval_scene_ties")
+
+
+@functools.lru_cache(maxsize=None)
+def ties_cases(part):
+    """The cases of part 'hand' or 'rand' as dicts: the inputs (ovl [nd, ng], ign_gt, ign_dt, score, dt_alpha, gt_alpha, dt_box,
+    dc_box) and what the reference's compute_statistics_jit returned for them.  hand: name, metric, min_overlap, thr, `a` (the
+    mode-A scores in ground-truth order) and `b` (len(thr), 4).  rand: `a` is a list over the combinations of `rand_comb`, `b` is
+    (combinations, thresholds, 4)."""
+    z = load("eval_ties.npz")
+    p = part + "_"
+    nd, ng, ndc = (z[p + k].astype(np.int64) for k in ("nd", "ng", "ndc"))
+    d0, g0, c0, p0 = (np.concatenate([[0], np.cumsum(v)]) for v in (nd, ng, ndc, nd * ng))
+    cases = []
+    for k in range(len(nd)):
+        c = dict(ovl=z[p + "ovl"][p0[k]:p0[k + 1]].reshape(nd[k], ng[k]), ign_gt=z[p + "ign_gt"][g0[k]:g0[k + 1]],
+                 ign_dt=z[p + "ign_dt"][d0[k]:d0[k + 1]], gt_alpha=z[p + "gt_alpha"][g0[k]:g0[k + 1]],
+                 dc_box=z[p + "dc_box"][c0[k]:c0[k + 1]])
+        for key in ("score", "dt_alpha", "dt_box"):
+            c[key] = z[p + key][d0[k]:d0[k + 1]]
+        cases.append(c)
+    if part == "hand":
+        t0, a0 = (np.concatenate([[0], np.cumsum(z[p + k])]) for k in ("nthr", "a_n"))
+        for k, c in enumerate(cases):
+            c.update(name=str(z["hand_name"][k]), metric=int(z["hand_metric"][k]), min_overlap=float(z["hand_min_overlap"][k]),
+                     thr=z["hand_thr"][t0[k]:t0[k + 1]], a=z["hand_a"][a0[k]:a0[k + 1]], b=z["hand_b"][t0[k]:t0[k + 1]])
+    else:
+        a0 = np.concatenate([[0], np.cumsum(z["rand_a_n"].ravel())]).reshape(-1)
+        n_comb = z["rand_comb"].shape[0]
+        for k, c in enumerate(cases):
+            c.update(name="rand_%d" % k, b=z["rand_b"][k],
+                     a=[z["rand_a"][a0[k * n_comb + m]:a0[k * n_comb + m + 1]] for m in range(n_comb)])
+    return cases
+
+
+def ties_comb(pairs):
+    """comb (n, 3) int32 and min_overlap (n,) for (metric, min_overlap) pairs: flag row 0, a similarity slot per metric-0 row
+    (compute_aos is on for metric 0, as in eval_class).  Returns comb, min_overlap, n_slots."""
+    comb, slots = [], 0
+    for metric, _ in pairs:
+        comb.append((int(metric), 0, slots if int(metric) == 0 else -1))
+        slots += int(metric) == 0
+    return np.array(comb, np.int32).reshape(-1, 3), np.array([mo for _, mo in pairs], np.float64), slots
+
+
+def ties_pack(cases):
+    """The cases as the images of one evaluator load: (packed, flags, overlaps).  One flag row with the cases' flags
+    concatenated; overlaps (3, P) float64 holds every case's matrix under all three metrics."""
+    nd = np.array([c["ovl"].shape[0] for c in cases], np.int64)
+    ng = np.array([c["ovl"].shape[1] for c in cases], np.int64)
+    ndc = np.array([len(c["dc_box"]) for c in cases], np.int64)
+    off = lambda v, t: np.concatenate([[0], np.cumsum(v)]).astype(t)                              # noqa: E731
+    cat = lambda k, w=None: np.ascontiguousarray(np.concatenate(                                  # noqa: E731
+        [np.asarray(c[k], np.float64).reshape((-1,) if w is None else (-1, w)) for c in cases], 0))
+    packed = {"n_img": len(cases), "gt_off": off(ng, np.int32), "dt_off": off(nd, np.int32), "dc_off": off(ndc, np.int32),
+              "pair_off": off(nd * ng, np.int64), "max_dt": int(nd.max()), "gt_alpha": cat("gt_alpha"), "dt_alpha": cat("dt_alpha"),
+              "dt_score": cat("score"), "dt_box2d": cat("dt_box", 4), "dc_box": cat("dc_box", 4)}
+    flags = {"gt": np.concatenate([c["ign_gt"] for c in cases]).astype(np.int8)[None],
+             "dt": np.concatenate([c["ign_dt"] for c in cases]).astype(np.int8)[None]}
+    flat = np.concatenate([c["ovl"].ravel() for c in cases]).astype(np.float64)
+    return packed, flags, np.ascontiguousarray(np.stack([flat] * 3))
+
+
+def ties_mode_a(ev, to_device, cases, pairs):
+    """Mode A of all `cases` as one load of evaluator `ev` under every (metric, min_overlap) of `pairs`: per case and pair the
+    kernel's row of that image compacted by != NO_DETECTION, i.e. the matched scores in ground-truth order."""
+    packed, flags, ovl = ties_pack(cases)
+    ev.load(packed, flags)
+    comb, mo, _ = ties_comb(pairs)
+    scores = np.asarray(ev.match_scores(to_device(ovl), comb, mo))
+    off = packed["gt_off"]
+    return [[row[off[i]:off[i + 1]][row[off[i]:off[i + 1]] != -1e7] for row in scores] for i in range(len(cases))]
+
+
+def ties_mode_b(ev, to_device, cases, pairs, thr):
+    """Mode B of all `cases` as one load: counts (pairs, thresholds, 3) summed over the cases and the similarity sums
+    (metric-0 pairs, thresholds), every pair at the thresholds `thr`."""
+    packed, flags, ovl = ties_pack(cases)
+    ev.load(packed, flags)
+    comb, mo, n_slots = ties_comb(pairs)
+    return ev.match_counts(to_device(ovl), comb, mo, [np.asarray(thr, np.float64)] * len(comb), n_slots)
+
+
+@functools.lru_cache(maxsize=None)
+def ties_scene():
+    """The end-to-end scene with duplicate scores: the `scene_*` keys of eval_ties.npz without the prefix."""
+    return {k[len("scene_"):]: v for k, v in load("eval_ties.npz").items() if k.startswith("scene_")}
